@@ -16,9 +16,14 @@ A "step" is one pass of the hot path over one batch of synthetic points already 
   other workloads (`--workload`): bounds (AABB only, 24 B/pt), las0_to_columns (configs[2]: 35 B interleaved LAS-0 ->
       10 columns, 70 B/pt), rawlas_to_columns (20 B raw records -> 10 columns with i32->f64 affine + bit fields, 55 B/pt).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with a `roofline` object.  A plain run sets up, warms up, times `--steps` steps and prints the line;
+everything else the line can carry runs only with `--full`, after the timed region: the CPU baseline and the oracle's check of the headline
+(`cpu_baseline`, `verified`), the other BASELINE configs and caller shapes (`configs2_las0_to_columns`, `configs4_knn16*`,
+`dropin_convert_then_bounds`, `chunked_rawlas_1MiB`), the 10^9-point leg (`north_star_1e9`), the sharded 10^9-point leg at N > 1
+(`configs3_1e9`) and `roofline.traffic` measured in the run under rocprofv3.
 The CPU baseline is the oracle (oracle/: faithful-shape single-thread restatement of the reference's Rust loops — the
 reference itself cannot be built offline) timed on the GPU box's host, rank 0, N = 1 only, on a bounded sample.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) for comparing two builds output for output.
 """
 import argparse
 import ctypes
@@ -117,7 +122,15 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-traffic-run", action="store_true", help="do not re-run the workload under rocprofv3 for roofline.traffic (the committed profiles/hbm_traffic.json figure is quoted instead)")
     p.add_argument("--cpu-sample-points", type=int, default=100_000_000, help="CPU baseline sample (default: the whole 10^8-point workload, ~10 s of CPU work)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the CPU baseline with the oracle's checks, the extra legs, the 10^9-point legs and the in-run "
+                        "rocprofv3 traffic pass (each still switched off by its --no-* option); a plain run measures the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy (f32 / f64, a fixed sample of at most 48 MB, see dump_outputs)")
+    args = p.parse_args()
+    if args.dump_outputs and args.workload == "voxelgrid_xyz":
+        p.error("--dump-outputs: voxelgrid_xyz allocates its output inside the step and keeps none (voxelgrid_xyz_async keeps it)")
+    return args
 
 
 def _native_oracle():
@@ -169,6 +182,43 @@ def _family_report(conv, dst_type, with_bounds, src_type=None):
     if choice in (0, 1):
         rep["ms_per_pass"] = {"las": round(ms[0], 4), "plan-specialised": round(ms[1], 4)}
     return rep
+
+
+DUMP_BYTES = 48 << 20  # sampled output columns of one dump; with the AABB the directory stays far below 64 MB
+DUMP_CHUNK = 1 << 14
+
+
+def dump_sample(count, bytes_per_point):
+    """The points --dump-outputs writes, as ascending ranges: all `count` when they fit DUMP_BYTES, else whole chunks of DUMP_CHUNK points at
+    offsets drawn with SEED -- the same points on every run with the same arguments."""
+    import numpy as np
+    fit = max(1, DUMP_BYTES // bytes_per_point)
+    if count <= fit:
+        return [range(0, count)]
+    chunk = min(DUMP_CHUNK, fit)
+    picks = np.random.default_rng(SEED).choice(count // chunk, size=fit // chunk, replace=False)
+    return [range(int(c) * chunk, (int(c) + 1) * chunk) for c in np.sort(picks)]
+
+
+def dump_outputs(out_dir, buf, count, bounds):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as out_dir/<name>.npy.  One file per attribute of the
+    output buffer's first `count` points over dump_sample (f32 stays f32, every other datatype becomes f64, byte arrays byte by byte), and
+    bounds.npy: the AABB of the last step, [min, max] x (x, y, z), for workloads whose step reduces one."""
+    import re
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if bounds is not None:
+        np.save(os.path.join(out_dir, "bounds.npy"), np.asarray(bounds, dtype=np.float64))
+    if buf is None or count == 0:
+        return
+    attrs = [m.attribute_definition() for m in buf.point_layout().attributes()]
+    kinds = [np.float32 if np.dtype(a.datatype().numpy_dtype()) == np.float32 else np.float64 for a in attrs]
+    out_bytes = sum(a.size() // np.dtype(a.datatype().numpy_dtype()).itemsize * np.dtype(k).itemsize for a, k in zip(attrs, kinds))
+    ranges = dump_sample(count, out_bytes)
+    for a, k in zip(attrs, kinds):
+        col = np.concatenate([buf.get_attribute_range(a, r) for r in ranges]).astype(k)
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", a.name()) + ".npy"), col)
 
 
 def measure_traffic_in_run(workload, n, kernel_substr, timeout_s=150):
@@ -1142,12 +1192,19 @@ def main():
         rec = rec.cpu()
         rec[3:] = -rec[3:]
     result = bounds_from_record(rec.cpu())
-    # BASELINE.json configs[3] made driver-visible: a driver that passes only `--gpus N` gets the weak-scaling line above AND this leg --
+    if args.dump_outputs and rank == 0:
+        if args.workload == "voxelgrid_xyz_async":
+            out_buf, out_count = vout, int(vcs[0].item())
+        else:
+            out_buf = locals().get("dst")
+            out_count = out_buf.len() if out_buf is not None else 0
+        dump_outputs(args.dump_outputs, out_buf, out_count, result if has_reduction else None)
+    # BASELINE.json configs[3] made driver-visible: a driver that passes `--gpus N --full` gets the weak-scaling line above AND this leg --
     # ONE 10^9-point cloud sharded by index range over the N ranks (strong scaling), the same fused step, the same exchange per step,
     # timed like the main region (barrier + synchronize before; each rank stops its clock when its steps and exchanges are done, then the barrier; max over ranks); never folded into `value`
     configs3 = None
     # (a single rank started under torchrun with PASTURE_FORCE_DIST=1 runs this leg too: the way the N > 1 code path is exercised on a 1-GPU box)
-    if (distributed and (world > 1 or os.environ.get("PASTURE_FORCE_DIST") == "1") and args.workload == "convert_affine_bounds"
+    if (args.full and distributed and (world > 1 or os.environ.get("PASTURE_FORCE_DIST") == "1") and args.workload == "convert_affine_bounds"
             and not args.global_points and not args.no_configs3):
         from pasture_amd.distributed import shard_range
         g3 = args.configs3_points
@@ -1215,9 +1272,9 @@ def main():
                             "one AABB all-reduce per step; wall time from the opening barrier to each rank's completion, max over ranks"}
         del s_src, s_dst
 
-    # BASELINE.json configs[2] and configs[4] made driver-visible (N = 1, default workload): measured after the timed region, never folded into `value`
+    # BASELINE.json configs[2] and configs[4] made driver-visible (--full, N = 1, default workload): measured after the timed region, never folded into `value`
     extra_legs, extra_checks = {}, {}
-    if world == 1 and not distributed and args.workload == "convert_affine_bounds" and not args.global_points and not args.no_extra_legs:
+    if args.full and world == 1 and not distributed and args.workload == "convert_affine_bounds" and not args.global_points and not args.no_extra_legs:
         src = dst = None
         try:
             rep, smp = leg_configs2(pa, las, cv, torch, stream, n, SEED)
@@ -1250,9 +1307,9 @@ def main():
         src = dst = None
 
     # north_star size made driver-visible: the same fused convert + AABB over 10^9 points (24 GB in, 24 GB out) on ONE GPU, measured in this
-    # run after the timed region (N = 1, default workload only); reported beside the headline, never folded into `value`
+    # run after the timed region (--full, N = 1, default workload only); reported beside the headline, never folded into `value`
     north_star = None
-    if (world == 1 and not args.no_north_star and args.workload == "convert_affine_bounds" and not args.global_points
+    if (args.full and world == 1 and not args.no_north_star and args.workload == "convert_affine_bounds" and not args.global_points
             and args.north_star_points > n):
         nn = args.north_star_points
         free_b, _total_b = torch.cuda.mem_get_info()
@@ -1308,7 +1365,7 @@ def main():
                                    f"{t.get('fetch_factor', 2)}: {t.get('calibrated_on', 'wide coalesced reads')}); NOT measured in this run")
             except Exception:
                 pass
-        if world == 1 and not distributed and args.workload == "convert_affine_bounds" and not args.no_traffic_run and not args.no_extra_legs and not args.global_points:  # (the default driver run only: the tools pass --no-extra-legs, some of them run under rocprofv3 themselves)
+        if args.full and world == 1 and not distributed and args.workload == "convert_affine_bounds" and not args.no_traffic_run and not args.no_extra_legs and not args.global_points:  # (a --full run of the default workload only: the tools pass --no-extra-legs, some of them run under rocprofv3 themselves)
             m = measure_traffic_in_run(args.workload, n, "vec3f64_stream2_kernel")
             if m is not None:
                 traffic, traffic_src = m
@@ -1368,7 +1425,7 @@ def main():
             line["north_star_1e9"] = north_star
         for name, rep in extra_legs.items():
             line[name] = rep
-        if world == 1 and not args.no_cpu_baseline and args.workload == "convert_affine_bounds":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "convert_affine_bounds":
             cb = cpu_baseline(args.workload, args.cpu_sample_points, extra_checks)
             if cb is not None:
                 line["cpu_baseline"] = cb

@@ -565,7 +565,7 @@ def test_bench_n_gt_1_code_path_with_one_forced_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update({"PASTURE_FORCE_DIST": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--configs3-points", "30000001", *common]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--configs3-points", "30000001", *common]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     got = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -677,7 +677,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     assert one.returncode == 0, one.stderr[-2000:]
     want = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--points", "5000000", "--configs3-points", "30000001", *common]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--points", "5000000", "--full", "--configs3-points", "30000001", *common]
     r = _run_ranks(cmd, env, lambda r: r.returncode == 0)
     assert r.returncode == 0, r.stderr[-3000:]
     got = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
