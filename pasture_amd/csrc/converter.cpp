@@ -194,7 +194,8 @@ bool specialised_kernel_ready(bool src_aos, uint64_t src_base, uint32_t src_stri
 // around the transformed one): the plan runs as an ordinary records -> records conversion -- every tile is read into LDS before it is
 // written and tiles are disjoint -- which lets the plan-specialised kernels take it (transform_attribute on a packed VectorBuffer)
 void execute_entries(bool src_aos, uint64_t src_base, uint32_t src_stride, bool dst_aos, uint64_t dst_base, uint32_t dst_stride,
-                     uint64_t n, const std::vector<PlanEntry>& entries, bool allow_lds, hipStream_t stream, double* bounds_out6, bool whole_records_in_place) {
+                     uint64_t n, const std::vector<PlanEntry>& entries, bool allow_lds, hipStream_t stream, double* bounds_out6, bool whole_records_in_place,
+                     const pstk::ZeroScan& folded) {
   if (n == 0 || entries.empty()) return;
   ensure_device();
   // interleaved in place (transform_attribute on a VectorBuffer): one record tile, transformed in LDS
@@ -214,7 +215,7 @@ void execute_entries(bool src_aos, uint64_t src_base, uint32_t src_stride, bool 
     }
     if (!pstk::launch_convert(plan, src_aos, dst_aos, use_lds, stream, &records))
       throw hip_failure("conversion kernel launch failed: ");
-    if (wants_bounds) pstk::launch_finalize_bounds(partials, records, bounds_out6, stream);
+    if (wants_bounds) pstk::launch_finalize_bounds(partials, records, bounds_out6, stream, folded);
   }
 }
 
@@ -458,6 +459,10 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "target PointLayout has no Position3D attribute");
     pos_slot = (int)(pm - c.to.members.data());
   }
+  // where the target's positions are: the last fold gives a +-0 bound the sign of the first zero there (zero_sign.hpp)
+  const pstk::ZeroScan folded = bounds_out6 ? pstk::ZeroScan{dst.columnar ? col_addr(dst, (size_t)pos_slot, t0) : aos_addr(dst, t0) + c.to.members[(size_t)pos_slot].offset,
+                                                             dst.columnar ? c.to.members[(size_t)pos_slot].size : c.to.size, n}
+                                            : pstk::ZeroScan{0, 0, 0};
   bool bounds_done = false;
 
   if (n > 0 && !src.columnar && !dst.columnar && !bounds_out6) {
@@ -493,7 +498,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
       double* partials = bounds_out6 ? (double*)workspace().partials(pstk::bounds_partials_bytes(grid)) : nullptr;
       if (!pstk::launch_las_transpose(c.las_typed_format, src.columnar, aos, cols.data(), (int)cols.size(), n, partials, stream))
         throw hip_failure("LAS transposition launch failed: ");
-      if (bounds_out6) pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream);
+      if (bounds_out6) pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream, folded);
       pstk::note_plan_kind(PST_PLAN_LAS);
       return;
     }
@@ -511,7 +516,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
       double* partials = bounds_out6 ? (double*)workspace().partials(pstk::bounds_partials_bytes(grid)) : nullptr;
       if (!pstk::launch_las_decode_aos(c.las_decode_format, aos_addr(src, s0), aos_addr(dst, t0), n, pos->xf->scale, pos->xf->offset, partials, stream))
         throw hip_failure("LAS decode launch failed: ");
-      if (bounds_out6) pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream);
+      if (bounds_out6) pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream, folded);
       pstk::note_plan_kind(PST_PLAN_LAS);
       return;
     }
@@ -522,7 +527,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     if (!pstk::launch_las_decode(c.las_decode_format, aos_addr(src, s0), n, cols.data(), (int)cols.size(), pos->xf->scale, pos->xf->offset, partials,
                                  stream))
       throw hip_failure("LAS decode launch failed: ");
-    if (bounds_out6) pstk::launch_finalize_bounds(partials, pstk::las_decode_grid(n), bounds_out6, stream);
+    if (bounds_out6) pstk::launch_finalize_bounds(partials, pstk::las_decode_grid(n), bounds_out6, stream, folded);
     pstk::note_plan_kind(PST_PLAN_LAS);
     return;
   }
@@ -596,7 +601,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
           throw hip_failure("column conversion launch failed: ");
         pstk::note_plan_kind(PST_PLAN_COLUMN);
         if (fuse_bounds) {
-          pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream);
+          pstk::launch_finalize_bounds(partials, grid, bounds_out6, stream, folded);
           bounds_done = true;
         }
         continue;
@@ -634,7 +639,8 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     }
     if (!generic.empty() && fused_done < n)
       execute_entries(!src.columnar, src.columnar ? 0 : aos_addr(src, s0 + fused_done), (uint32_t)c.from.size, !dst.columnar,
-                      dst.columnar ? 0 : aos_addr(dst, t0 + fused_done), (uint32_t)c.to.size, n - fused_done, generic, true, stream, fuse_expr ? nullptr : bounds_out6);
+                      dst.columnar ? 0 : aos_addr(dst, t0 + fused_done), (uint32_t)c.to.size, n - fused_done, generic, true, stream, fuse_expr ? nullptr : bounds_out6,
+                      false, folded);
   }
   PST_HIP_CHECK(hipGetLastError());
   if (bounds_out6 && !bounds_done) {

@@ -30,8 +30,11 @@ bool prepare_convert(const ConvertPlan& plan, bool src_aos, bool dst_aos, std::s
 bool launch_convert_fused_expressions(const ConvertPlan& plan, bool src_aos, bool dst_aos, hipStream_t stream, uint64_t* done, std::string* error);
 bool convert_specialised_ready(const ConvertPlan& plan, bool src_aos, bool dst_aos);
 size_t bounds_partials_bytes(unsigned n_records);
-// fold n_records per-block {min xyz, max xyz} records into out6
-void launch_finalize_bounds(double* partials, unsigned n_records, double* out6, hipStream_t stream);
+// The elements a fold ran over, for the sign of a bound that comes out as +-0 (zero_sign.hpp): element e's components at base + e * stride.
+// n = 0: none (the bound keeps whichever zero the fold returned).
+struct ZeroScan { uint64_t base, stride, n; };
+// fold n_records per-block {min xyz, max xyz} records into out6; `folded` = the Vec3f64 values those records were folded from
+void launch_finalize_bounds(double* partials, unsigned n_records, double* out6, hipStream_t stream, const ZeroScan& folded);
 // pst_bounds_record_set_form: records at these addresses leave the last fold kernel as {min, -max}
 void set_bounds_record_form(const void* device_rec6, int form);
 bool bounds_record_negates_max(const void* device_rec6);

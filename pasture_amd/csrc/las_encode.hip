@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "las_device.hpp"
 #include "tile_io.hpp"
+#include "zero_sign.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -360,11 +361,13 @@ __global__ __launch_bounds__(kBlock) void las_encode_kernel(const EncodeArgs a) 
   if (threadIdx.x < kReturnSlots) a.partial_counts[(uint64_t)blockIdx.x * kReturnSlots + threadIdx.x] = hist[threadIdx.x];
 }
 
-// Folds partials [0, n_in) into one record per block (block b takes b, b + gridDim.x, ...).
+// Folds partials [0, n_in) into one record per block (block b takes b, b + gridDim.x, ...).  positions: the Vec3f64 positions encoded (n = 0 on
+// a first level); a bound that comes out as +-0 is the header's seed when that is a zero (it comes first), else the first zero of the positions.
 __global__ __launch_bounds__(kBlock) void las_encode_fold_kernel(const double* __restrict__ partial_bounds,
                                                                  const unsigned long long* __restrict__ partial_counts, uint32_t n_in,
                                                                  double* __restrict__ out_bounds, unsigned long long* __restrict__ out_counts,
-                                                                 double s0, double s1, double s2, double t0, double t1, double t2) {
+                                                                 double s0, double s1, double s2, double t0, double t1, double t2,
+                                                                 const pstk::ZeroScan positions) {
   double mn[3] = {s0, s1, s2}, mx[3] = {t0, t1, t2};
   for (uint32_t b = blockIdx.x + gridDim.x * threadIdx.x; b < n_in; b += gridDim.x * kBlock) {
 #pragma unroll
@@ -375,6 +378,16 @@ __global__ __launch_bounds__(kBlock) void las_encode_fold_kernel(const double* _
   }
   __shared__ double scratch[(kBlock / 64) * 6];
   block_reduce_minmax<double, 3>(mn, mx, scratch);
+  uint32_t settled = 0;
+  if (threadIdx.x == 0) {
+    const double seeds[6] = {s0, s1, s2, t0, t1, t2};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (mn[c] == 0.0 && seeds[c] == 0.0) { mn[c] = seeds[c]; settled |= 1u << c; }
+      if (mx[c] == 0.0 && seeds[3 + c] == 0.0) { mx[c] = seeds[3 + c]; settled |= 1u << (3 + c); }
+    }
+  }
+  zero_bounds_in_index_order<double, double, 3>(positions, mn, mx, settled);
   if (threadIdx.x == 0) {
     double* o = out_bounds + (uint64_t)blockIdx.x * 6;
     o[0] = mn[0]; o[1] = mn[1]; o[2] = mn[2]; o[3] = mx[0]; o[4] = mx[1]; o[5] = mx[2];
@@ -468,13 +481,14 @@ bool launch_las_encode(int format, const uint64_t* attr_base, const uint32_t* at
   const unsigned long long* in_c = pc;
   if (n_in > 4 * kFoldGrid) {  // two-level fold: 64 blocks first
     hipLaunchKernelGGL(las_encode_fold_kernel, dim3(kFoldGrid), dim3(kBlock), 0, stream, in_b, in_c, n_in, pb + (size_t)kMaxGrid * 6,
-                       pc + (size_t)kMaxGrid * kReturnSlots, bounds_in[0], bounds_in[1], bounds_in[2], bounds_in[3], bounds_in[4], bounds_in[5]);
+                       pc + (size_t)kMaxGrid * kReturnSlots, bounds_in[0], bounds_in[1], bounds_in[2], bounds_in[3], bounds_in[4], bounds_in[5],
+                       ZeroScan{0, 0, 0});
     in_b = pb + (size_t)kMaxGrid * 6;
     in_c = pc + (size_t)kMaxGrid * kReturnSlots;
     n_in = kFoldGrid;
   }
   hipLaunchKernelGGL(las_encode_fold_kernel, dim3(1), dim3(kBlock), 0, stream, in_b, in_c, n_in, out_bounds, out_counts, bounds_in[0], bounds_in[1],
-                     bounds_in[2], bounds_in[3], bounds_in[4], bounds_in[5]);
+                     bounds_in[2], bounds_in[3], bounds_in[4], bounds_in[5], ZeroScan{attr_base[0], attr_stride[0], n});
   return hipGetLastError() == hipSuccess;
 }
 

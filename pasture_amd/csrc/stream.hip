@@ -23,6 +23,7 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "stream_tile.hpp"
+#include "zero_sign.hpp"
 
 #include <algorithm>
 #include <mutex>
@@ -201,9 +202,12 @@ __global__ __launch_bounds__(kBlock) void vec3f64_stream_kernel(const StreamPara
 
 // Folds per-block records: block b reduces records [b*chunk, (b+1)*chunk) into out[b] = {min[NV], max[NV]}.
 // Launched with one block (chunk >= n_records) for the final fold, or as a first level when there are many records.
-template <typename T, int NV>
+// folded: the elements (components of type S) the records came from -- the final fold gives a +-0 bound the sign of the first zero in index order
+// (zero_sign.hpp); n = 0 on a first level.
+template <typename T, int NV, typename S = T>
 __global__ __launch_bounds__(kBlock) void finalize_minmax_kernel(const T* __restrict__ partials, uint32_t n_records, uint32_t chunk,
-                                                                 T* __restrict__ out, T seed_min, T seed_max, uint32_t negate_max = 0) {
+                                                                 T* __restrict__ out, T seed_min, T seed_max, uint32_t negate_max,
+                                                                 const pstk::ZeroScan folded) {
   T mn[NV], mx[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) { mn[i] = seed_min; mx[i] = seed_max; }
@@ -218,6 +222,7 @@ __global__ __launch_bounds__(kBlock) void finalize_minmax_kernel(const T* __rest
   }
   __shared__ T scratch[(kBlock / 64) * 2 * NV];
   block_reduce_minmax<T, NV>(mn, mx, scratch);
+  if constexpr (std::is_floating_point<T>::value) zero_bounds_in_index_order<S, T, NV>(folded, mn, mx);
   if (threadIdx.x == 0) {
     T* o = out + (uint64_t)blockIdx.x * 2 * NV;
 #pragma unroll
@@ -228,19 +233,19 @@ __global__ __launch_bounds__(kBlock) void finalize_minmax_kernel(const T* __rest
 // two-level fold when there are many records (one-tile-per-block launches); `partials` must have room for
 // n_records + kFoldBlocks records
 constexpr uint32_t kFoldBlocks = 128;
-template <typename T, int NV>
-void launch_finalize(T* partials, uint32_t n_records, T* out, T seed_min, T seed_max, hipStream_t stream, bool negate_max = false) {
-  const uint32_t neg = negate_max ? 1u : 0u;  // (the LAST level only)
+template <typename T, int NV, typename S = T>
+void launch_finalize(T* partials, uint32_t n_records, T* out, T seed_min, T seed_max, hipStream_t stream, bool negate_max, const pstk::ZeroScan& folded) {
+  const uint32_t neg = negate_max ? 1u : 0u;  // (the LAST level only, like the zero-sign lookup)
   if (n_records > 4096) {
     const uint32_t chunk = (n_records + kFoldBlocks - 1) / kFoldBlocks;
     T* level1 = partials + (uint64_t)n_records * 2 * NV;
-    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV>), dim3(kFoldBlocks), dim3(kBlock), 0, stream, (const T*)partials, n_records, chunk, level1,
-                       seed_min, seed_max, 0u);
-    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV>), dim3(1), dim3(kBlock), 0, stream, (const T*)level1, kFoldBlocks, kFoldBlocks, out,
-                       seed_min, seed_max, neg);
+    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV, S>), dim3(kFoldBlocks), dim3(kBlock), 0, stream, (const T*)partials, n_records, chunk, level1,
+                       seed_min, seed_max, 0u, pstk::ZeroScan{0, 0, 0});
+    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV, S>), dim3(1), dim3(kBlock), 0, stream, (const T*)level1, kFoldBlocks, kFoldBlocks, out,
+                       seed_min, seed_max, neg, folded);
   } else {
-    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV>), dim3(1), dim3(kBlock), 0, stream, (const T*)partials, n_records, n_records, out, seed_min,
-                       seed_max, neg);
+    hipLaunchKernelGGL((finalize_minmax_kernel<T, NV, S>), dim3(1), dim3(kBlock), 0, stream, (const T*)partials, n_records, n_records, out, seed_min,
+                       seed_max, neg, folded);
   }
 }
 
@@ -285,13 +290,16 @@ template <typename T> struct Identity {
 
 template <typename T, int NCOMP>
 void launch_minmax_typed(const ReduceParams& p, bool acc_f64, void* out, unsigned grid, hipStream_t stream) {
+  // (integer elements have no -0: their zero bounds are +0 whichever element they came from)
+  const pstk::ZeroScan folded = std::is_floating_point<T>::value ? pstk::ZeroScan{(uint64_t)p.base, p.stride, p.n} : pstk::ZeroScan{0, 0, 0};
   if (acc_f64) {
     hipLaunchKernelGGL((strided_minmax_kernel<T, double, NCOMP>), dim3(grid), dim3(kBlock), 0, stream, p, kF64Max, -kF64Max);
-    launch_finalize<double, NCOMP>((double*)p.partials, grid, (double*)out, kF64Max, -kF64Max, stream, NCOMP == 3 && bounds_record_negates_max(out));
+    launch_finalize<double, NCOMP, T>((double*)p.partials, grid, (double*)out, kF64Max, -kF64Max, stream, NCOMP == 3 && bounds_record_negates_max(out),
+                                      folded);
   } else {
     hipLaunchKernelGGL((strided_minmax_kernel<T, T, NCOMP>), dim3(grid), dim3(kBlock), 0, stream, p, Identity<T>::min_seed(),
                        Identity<T>::max_seed());
-    launch_finalize<T, NCOMP>((T*)p.partials, grid, (T*)out, Identity<T>::min_seed(), Identity<T>::max_seed(), stream);
+    launch_finalize<T, NCOMP>((T*)p.partials, grid, (T*)out, Identity<T>::min_seed(), Identity<T>::max_seed(), stream, false, folded);
   }
 }
 
@@ -441,7 +449,9 @@ void launch_vec3f64_stream(const double* src, double* dst, uint64_t n_points, co
     if (mode & 1u) hipLaunchKernelGGL((vec3f64_stream_kernel<true, false, true, kStreamLoads, true, true>), dim3(grid), dim3(kBlock), 0, stream, p);
     else hipLaunchKernelGGL((vec3f64_stream_kernel<false, false, true, kStreamLoads, true, true>), dim3(grid), dim3(kBlock), 0, stream, p);
   }
-  if (bounds) launch_finalize<double, 3>(partials, grid, out6, kF64Max, -kF64Max, stream, bounds_record_negates_max(out6));
+  if (bounds)
+    launch_finalize<double, 3>(partials, grid, out6, kF64Max, -kF64Max, stream, bounds_record_negates_max(out6),
+                               pstk::ZeroScan{(uint64_t)(uintptr_t)(write ? (const double*)dst : src), 24, n_points});
 }
 
 size_t centroid_partials_bytes() { return (size_t)reduce_grid() * 8 * sizeof(double); }
@@ -453,8 +463,8 @@ unsigned launch_centroid(const uint8_t* base, uint64_t stride, uint64_t n, doubl
 }
 
 size_t bounds_partials_bytes(unsigned n_records) { return (size_t)(n_records + kFoldBlocks) * 6 * sizeof(double); }
-void launch_finalize_bounds(double* partials, unsigned n_records, double* out6, hipStream_t stream) {
-  launch_finalize<double, 3>(partials, n_records, out6, kF64Max, -kF64Max, stream, bounds_record_negates_max(out6));
+void launch_finalize_bounds(double* partials, unsigned n_records, double* out6, hipStream_t stream, const ZeroScan& folded) {
+  launch_finalize<double, 3>(partials, n_records, out6, kF64Max, -kF64Max, stream, bounds_record_negates_max(out6), folded);
 }
 
 void launch_minmax(const uint8_t* base, uint64_t stride, uint64_t n, uint32_t ct, uint32_t ncomp, bool acc_f64, void* partials, void* out,

@@ -312,8 +312,9 @@ def _fold_header(header_bounds, max_return, n_chunks, dev_bounds, dev_counts):
         bad = int(cc[:, 0].sum())
         if bad:
             raise PasturePanic(ERR_RANGE, f"write_position_as_las_position: Position is out of bounds given the current LAS offset and scale! ({bad} positions)")
-        mn, mx = cb[:, :3].min(dim=0).values.tolist(), cb[:, 3:].max(dim=0).values.tolist()
-        hb = [min(hb[i], mn[i]) for i in range(3)] + [max(hb[3 + i], mx[i]) for i in range(3)]
+        # chunk order with strict compares (update_bounds_in_las_header, raw_writers.rs:28-48): among equal bounds -- +0 and -0 -- the first stays
+        for r in cb.tolist():
+            hb = [r[i] if r[i] < hb[i] else hb[i] for i in range(3)] + [r[3 + i] if r[3 + i] > hb[3 + i] else hb[3 + i] for i in range(3)]
         counts = [int(x) for x in cc[:, 1:max_return + 1].sum(dim=0).tolist()]
     return (tuple(hb[:3]), tuple(hb[3:])), counts
 
