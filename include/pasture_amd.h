@@ -379,6 +379,53 @@ int pst_voxelgrid_plan_create(const pst_buffer* buffer, double leafsize_x, doubl
 int pst_voxelgrid_plan_destroy(pst_voxel_plan* plan);
 int pst_voxelgrid_filter_async(pst_voxel_plan* plan, const pst_buffer* buffer, pst_buffer* filtered, size_t dst_first, uint64_t* device_count_and_status);
 
+/* ---- RANSAC plane / line segmentation (pasture-algorithms/src/segmentation.rs:117-370) ------------------------------------------
+ * ransac_plane_serial / ransac_line_serial with the two halves of the reference's loop separated at the random numbers, which come from
+ * rand::thread_rng() there and cannot be reproduced: *_fit scores hypotheses built from point indices the CALLER names, the sampler
+ * produces such indices from a seed, and the seeded entry points are the sampler followed by *_fit, nothing more.
+ * Position3D must be stored as Vec3f64 (view_attribute::<Vector3<f64>>: anything else -> PST_ERR_MISSING_ATTRIBUTE); interleaved or columnar,
+ * owned, sliced or external.  Models cross the boundary as plain arrays: double plane[4] = a, b, c, d of ax + by + cz + d = 0 (not
+ * normalised); double line[6] = first xyz, second xyz.
+ *   plane from (i1, i2, i3):  v1 = p2 - p1, v2 = p3 - p1, n = v1 x v2, d = -(n . p1)                                   (:60-75)
+ *   plane inlier:  |a*x + b*y + c*z + d| / sqrt(a*a + b*b + c*c) < distance_threshold                                    (:31-35)
+ *   line inlier:   |(second - first) x (first - p)| / |second - first| < distance_threshold                              (:39-44)
+ * every operation a separately rounded f64 operation, left to right, the division included; cross = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x), dot = (a.x*b.x + a.y*b.y) + a.z*b.z, norm = sqrt((x*x + y*y) + z*z) (asserted of nalgebra, unverified).
+ * Degenerate hypotheses (collinear or coincident samples) and NaN coordinates fall out of IEEE arithmetic: no inliers.  The ranking of a
+ * hypothesis is its number of inliers; the result is the hypothesis with the highest ranking, the LAST such iteration on ties
+ * (Iterator::max_by of ransac_*_serial; rayon's choice in *_par is unspecified).
+ * Status codes: fewer than 3 (plane) / 2 (line) points -> PST_ERR_TOO_FEW_POINTS (the reference's panics :119-121, :98); iterations == 0 ->
+ * PST_ERR_INVALID_ARGUMENT (unwrap of an empty max_by); a sample index >= len -> PST_ERR_RANGE; equal indices inside one hypothesis ->
+ * PST_ERR_INVALID_ARGUMENT (the reference's redraw loops make them impossible); 2^32 - 1 points and more, or 2^32 iterations and more ->
+ * PST_ERR_UNSUPPORTED.  Null arguments and iterations == 0 are answered before a device is looked for. */
+/* Host only, no device needed.  Fills out_indices[iterations * per_hypothesis] (per_hypothesis = 3 plane, 2 line).  The recipe: ONE counter c
+ * per call starts at 0 and advances by one with every draw; draw() = (splitmix64(seed ^ c) * n_points) >> 64 (the 128-bit product; splitmix64 =
+ * the finaliser of pst_buffer_synth_fill: x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) *
+ * 0x94D049BB133111EB; x ^ x >> 31).  Per iteration: r1 = draw(); r2 = draw(), redrawn while r2 == r1; for a plane r3 = draw(), redrawn while
+ * r3 == r2 or r3 == r1 (:50-58, :82-87).  n_points < per_hypothesis -> PST_ERR_TOO_FEW_POINTS (the loops would not end). */
+int pst_ransac_sample_indices(uint64_t seed, size_t n_points, size_t iterations, uint32_t per_hypothesis, uint64_t* out_indices);
+/* samples: host, iterations * 3 (plane) / * 2 (line) point indices.  Returns the winning model, its ranking, (optional) which iteration won and
+ * (optional) rankings[iterations] of every hypothesis.  The positions are read once per batch of hypotheses, not once per hypothesis. */
+int pst_ransac_plane_fit(const pst_buffer* b, double distance_threshold, const uint64_t* samples, size_t iterations, double plane[4], uint64_t* ranking,
+                         size_t* best_iteration, uint64_t* rankings);
+int pst_ransac_line_fit(const pst_buffer* b, double distance_threshold, const uint64_t* samples, size_t iterations, double line[6], uint64_t* ranking,
+                        size_t* best_iteration, uint64_t* rankings);
+/* pst_ransac_sample_indices(seed, len, iterations, 3 | 2) followed by *_fit */
+int pst_ransac_plane(const pst_buffer* b, double distance_threshold, size_t iterations, uint64_t seed, double plane[4], uint64_t* ranking);
+int pst_ransac_line(const pst_buffer* b, double distance_threshold, size_t iterations, uint64_t seed, double line[6], uint64_t* ranking);
+/* The inliers of a model (the Vec<usize> of the reference's result), ascending.  *count = their number -- equal to the ranking *_fit returned
+ * for the same model and threshold (one device function serves every kernel).  indices (host, optional) receives them when they fit
+ * `capacity`; more inliers than that -> PST_ERR_RANGE with *count still set.  An empty buffer has none (answered on the host). */
+int pst_plane_inliers(const pst_buffer* b, const double plane[4], double distance_threshold, uint64_t* indices, size_t capacity, uint64_t* count);
+int pst_line_inliers(const pst_buffer* b, const double line[6], double distance_threshold, uint64_t* indices, size_t capacity, uint64_t* count);
+/* The same predicate as a byte mask (1 = inlier) of len bytes in DEVICE memory, stream-ordered, no host synchronisation: what
+ * pst_buffer_filter_into(..., PST_MEM_DEVICE, ranking, ...) and pst_buffer_filter_into_async take. */
+int pst_plane_inlier_mask_device(const pst_buffer* b, const double plane[4], double distance_threshold, uint8_t* device_mask);
+int pst_line_inlier_mask_device(const pst_buffer* b, const double line[6], double distance_threshold, uint8_t* device_mask);
+/* The scoring kernel's seams (tests place their sizes around them; each pointer optional): points one wave holds in registers, points per
+ * workgroup, workgroups per compute unit of one grid pass, hypotheses scored per pass over the positions.  Host only. */
+int pst_ransac_kernel_shape(uint32_t* points_per_wave, uint32_t* points_per_block, uint32_t* blocks_per_cu, uint32_t* batch);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -79,6 +79,8 @@ _PP = C.POINTER(C.c_void_p)
 _DT = C.POINTER(DataTypeStruct)
 _SZ = C.c_size_t
 _D3 = C.POINTER(C.c_double)
+_U64P = C.POINTER(C.c_uint64)
+_U32P = C.POINTER(C.c_uint32)
 
 # name -> argtypes; every function returns int except last_error
 _SHARED_SIGNATURES = {
@@ -178,6 +180,16 @@ _PRODUCT_SIGNATURES = {
     "transform_attribute_expr": [_P, C.c_char_p, _DT, C.c_char_p, _PP, _SZ],
     "buffer_filter_expr": [_P, C.c_char_p, _PP, _SZ, C.c_uint32, _PP],
     "expr_source": [C.c_int, _P, _DT, _DT, C.c_int, C.c_char_p, C.c_char_p, _SZ, C.POINTER(_SZ)],
+    "ransac_sample_indices": [C.c_uint64, _SZ, _SZ, C.c_uint32, _U64P],
+    "ransac_plane_fit": [_P, C.c_double, _U64P, _SZ, _D3, _U64P, C.POINTER(_SZ), _U64P],
+    "ransac_line_fit": [_P, C.c_double, _U64P, _SZ, _D3, _U64P, C.POINTER(_SZ), _U64P],
+    "ransac_plane": [_P, C.c_double, _SZ, C.c_uint64, _D3, _U64P],
+    "ransac_line": [_P, C.c_double, _SZ, C.c_uint64, _D3, _U64P],
+    "plane_inliers": [_P, _D3, C.c_double, _U64P, _SZ, _U64P],
+    "line_inliers": [_P, _D3, C.c_double, _U64P, _SZ, _U64P],
+    "plane_inlier_mask_device": [_P, _D3, C.c_double, _P],
+    "line_inlier_mask_device": [_P, _D3, C.c_double, _P],
+    "ransac_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

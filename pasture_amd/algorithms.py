@@ -5,6 +5,7 @@
   transform_attribute  pasture-core/src/containers/point_buffer.rs:391-404 (closed-set transformations)
   compute_normals    pasture-algorithms/src/normal_estimation.rs:79-130
   compute_centroid   pasture-algorithms/src/normal_estimation.rs:198-237
+  ransac_plane / ransac_line  pasture-algorithms/src/segmentation.rs:117-370
 """
 from __future__ import annotations
 
@@ -185,3 +186,143 @@ class NormalsPlan:
             self.destroy()
         except Exception:
             pass
+
+
+# ---- RANSAC plane / line segmentation, pasture-algorithms/src/segmentation.rs ------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Plane:
+    """segmentation.rs:19-28: ax + by + cz + d = 0 (not normalised); ranking = number of inliers."""
+    a: float
+    b: float
+    c: float
+    d: float
+    ranking: int
+
+    def coefficients(self) -> Tuple[float, float, float, float]:
+        return (self.a, self.b, self.c, self.d)
+
+
+@dataclass(frozen=True)
+class Line:
+    """segmentation.rs:10-17: the line through `first` and `second`; ranking = number of inliers."""
+    first: Tuple[float, float, float]
+    second: Tuple[float, float, float]
+    ranking: int
+
+    def coefficients(self) -> Tuple[float, ...]:
+        return tuple(self.first) + tuple(self.second)
+
+
+_U64P = C.POINTER(C.c_uint64)
+
+
+def _u64(a: np.ndarray):
+    return a.ctypes.data_as(_U64P)
+
+
+def ransac_sample_indices(seed: int, n_points: int, iterations: int, per_hypothesis: int, api=None) -> np.ndarray:
+    """The seeded sampler (host only): (iterations, per_hypothesis) point indices, per_hypothesis = 3 for planes, 2 for lines; the recipe is in
+    include/pasture_amd.h (pst_ransac_sample_indices)."""
+    from ._capi import product_api
+    out = np.zeros((iterations, per_hypothesis), dtype=np.uint64)
+    (api or product_api()).ransac_sample_indices(seed & 0xFFFFFFFFFFFFFFFF, n_points, iterations, per_hypothesis, _u64(out))
+    return out
+
+
+def _ransac_fit(buffer: _Buffer, line: bool, distance_threshold: float, samples, return_rankings: bool):
+    per = 2 if line else 3
+    samples = np.ascontiguousarray(np.asarray(samples, dtype=np.uint64))
+    if samples.ndim != 2 or samples.shape[1] != per:
+        raise ValueError(f"samples must have shape (iterations, {per})")
+    iterations = samples.shape[0]
+    model = (C.c_double * 6)()
+    ranking, best = C.c_uint64(), C.c_size_t()
+    rankings = np.zeros(iterations, dtype=np.uint64) if return_rankings else None
+    fn = buffer.api.ransac_line_fit if line else buffer.api.ransac_plane_fit
+    fn(buffer._h, distance_threshold, _u64(samples), iterations, model, C.byref(ranking), C.byref(best), _u64(rankings) if return_rankings else None)
+    m = Line(tuple(model[0:3]), tuple(model[3:6]), ranking.value) if line else Plane(model[0], model[1], model[2], model[3], ranking.value)
+    return m, best.value, rankings
+
+
+def ransac_plane_fit(buffer: _Buffer, distance_threshold: float, samples, return_rankings: bool = False):
+    """Scores the plane hypotheses through the point triples `samples` (iterations, 3): (Plane, winning iteration[, rankings of all])."""
+    m, best, rk = _ransac_fit(buffer, False, distance_threshold, samples, return_rankings)
+    return (m, best, rk) if return_rankings else (m, best)
+
+
+def ransac_line_fit(buffer: _Buffer, distance_threshold: float, samples, return_rankings: bool = False):
+    m, best, rk = _ransac_fit(buffer, True, distance_threshold, samples, return_rankings)
+    return (m, best, rk) if return_rankings else (m, best)
+
+
+def _model_array(model, line: bool):
+    v = model.coefficients() if isinstance(model, (Plane, Line)) else tuple(model)
+    if len(v) != (6 if line else 4):
+        raise ValueError("a plane has 4 coefficients, a line 6")
+    return (C.c_double * 6)(*v)
+
+
+def _inliers(buffer: _Buffer, line: bool, model, distance_threshold: float, capacity: Optional[int]) -> np.ndarray:
+    fn = buffer.api.line_inliers if line else buffer.api.plane_inliers
+    arr = _model_array(model, line)
+    count = C.c_uint64()
+    if capacity is None:
+        fn(buffer._h, arr, distance_threshold, None, 0, C.byref(count))
+        capacity = count.value
+    out = np.zeros(capacity, dtype=np.uint64)
+    fn(buffer._h, arr, distance_threshold, _u64(out), capacity, C.byref(count))
+    return out[:count.value]
+
+
+def plane_inliers(buffer: _Buffer, plane, distance_threshold: float, capacity: Optional[int] = None) -> np.ndarray:
+    """Indices (ascending, uint64) of the points closer to `plane` (a Plane or (a, b, c, d)) than distance_threshold."""
+    return _inliers(buffer, False, plane, distance_threshold, capacity)
+
+
+def line_inliers(buffer: _Buffer, line, distance_threshold: float, capacity: Optional[int] = None) -> np.ndarray:
+    return _inliers(buffer, True, line, distance_threshold, capacity)
+
+
+def plane_inlier_mask(buffer: _Buffer, plane, distance_threshold: float, device_mask_ptr: int) -> None:
+    """Stream-ordered: writes len(buffer) bytes (1 = inlier) to DEVICE memory at device_mask_ptr -- the mask filter_into / filter_into_async take
+    as (device_mask_ptr, 'device')."""
+    buffer.api.plane_inlier_mask_device(buffer._h, _model_array(plane, False), distance_threshold, C.c_void_p(int(device_mask_ptr)))
+
+
+def line_inlier_mask(buffer: _Buffer, line, distance_threshold: float, device_mask_ptr: int) -> None:
+    buffer.api.line_inlier_mask_device(buffer._h, _model_array(line, True), distance_threshold, C.c_void_p(int(device_mask_ptr)))
+
+
+def _ransac(buffer: _Buffer, line: bool, distance_threshold: float, num_of_iterations: int, seed: int, samples):
+    if samples is None:
+        model = (C.c_double * 6)()
+        ranking = C.c_uint64()
+        fn = buffer.api.ransac_line if line else buffer.api.ransac_plane
+        fn(buffer._h, distance_threshold, num_of_iterations, seed & 0xFFFFFFFFFFFFFFFF, model, C.byref(ranking))
+        m = Line(tuple(model[0:3]), tuple(model[3:6]), ranking.value) if line else Plane(model[0], model[1], model[2], model[3], ranking.value)
+    else:
+        samples = np.asarray(samples, dtype=np.uint64)
+        if samples.shape[0] != num_of_iterations:
+            raise ValueError("samples must hold num_of_iterations hypotheses")
+        m = _ransac_fit(buffer, line, distance_threshold, samples, False)[0]
+    return m, _inliers(buffer, line, m, distance_threshold, m.ranking)
+
+
+def ransac_plane(buffer: _Buffer, distance_threshold: float, num_of_iterations: int, seed: int = 0, samples=None):
+    """ransac_plane_serial, segmentation.rs:233-256: (Plane, indices of its inliers as uint64, ascending).  The reference's hypotheses come from
+    rand::thread_rng(); here from the seeded sampler (ransac_sample_indices) or from `samples` (num_of_iterations, 3)."""
+    return _ransac(buffer, False, distance_threshold, num_of_iterations, seed, samples)
+
+
+def ransac_line(buffer: _Buffer, distance_threshold: float, num_of_iterations: int, seed: int = 0, samples=None):
+    """ransac_line_serial, segmentation.rs:341-370: (Line, indices of its inliers)."""
+    return _ransac(buffer, True, distance_threshold, num_of_iterations, seed, samples)
+
+
+def ransac_kernel_shape(api=None) -> dict:
+    """The scoring kernel's seams: points per wave, per workgroup, workgroups per compute unit of one grid pass, hypotheses per pass."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(4)]
+    (api or product_api()).ransac_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_wave", "points_per_block", "blocks_per_cu", "batch"), (x.value for x in v)))

@@ -174,4 +174,23 @@ bool voxel_grid_reduce(VoxelGridState* st, const uint64_t* src_addr, const uint3
                        const uint32_t* reduce, const uint32_t* kind, int n_attrs, uint64_t dst_first, hipStream_t stream);
 void voxel_grid_free(VoxelGridState* st);
 
+
+// RANSAC plane / line segmentation (ransac.hip).  The kernels' seams, which the tests place their sizes around (pst_ransac_kernel_shape):
+constexpr uint32_t kRansacPointsPerWave = 256;    // one wave scores a tile of this many points, four per lane in registers
+constexpr uint32_t kRansacPointsPerBlock = 1024;  // four waves; also the tile of the ordered index compaction
+constexpr uint32_t kRansacBlocksPerCu = 8;        // grid = min(blocks needed, CUs x this): one grid pass covers CUs x 8 x 1024 points
+constexpr uint32_t kRansacBatch = 1024;           // hypotheses scored per pass over the positions (per-wave LDS counters: 4 KiB)
+size_t ransac_record_bytes(bool line);
+// table -> scoring (one pass over the positions per kRansacBatch hypotheses) -> arg-max.  recs: iterations records, rank: iterations u64,
+// out8: {best iteration, its ranking, model doubles x 6} (64 bytes).  samples_dev: iterations x 3 (plane) / x 2 (line) point indices.
+bool ransac_fit(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, double thr, const uint64_t* samples_dev, uint64_t iterations, void* recs,
+                unsigned long long* rank, unsigned long long* out8, hipStream_t stream);
+// model: plane a b c d / line first xyz, second xyz.  rec_scratch: ransac_record_bytes() of device memory.
+bool ransac_model_record(bool line, const double* model, double thr, void* rec_scratch, hipStream_t stream);
+bool ransac_mask(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const double* model, double thr, void* rec_scratch, uint8_t* mask_dev,
+                 hipStream_t stream);
+// write = false: counts[block] = inliers among the block's kRansacPointsPerBlock points; write = true: the indices, ascending, at offsets[block] ..
+bool ransac_index_pass(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const void* rec, uint32_t* counts, const unsigned long long* offsets,
+                       unsigned long long* indices, bool write, hipStream_t stream);
+
 }  // namespace pstk

@@ -1,0 +1,252 @@
+// pst_ransac_* / pst_*_inliers / pst_*_inlier_mask_device: sampler, argument checks and plumbing for ransac.hip.
+// Reference: pasture-algorithms/src/segmentation.rs:47-94 (hypotheses and their redraw loops), :117-370 (ransac_{plane,line}_{serial,par}).
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "device_sort.hpp"
+#include "runtime.hpp"
+
+using namespace pst;
+
+namespace {
+
+// the finaliser synth.hip uses for pst_buffer_synth_fill
+inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// The sampler's recipe (include/pasture_amd.h): ONE counter c, starting at 0, feeds every draw of a call and advances by one per draw, redraws
+// included; draw = (splitmix64(seed ^ c) * n) >> 64 from the 128-bit product.
+void sample_indices(uint64_t seed, uint64_t n, size_t iterations, uint32_t per, uint64_t* out) {
+  uint64_t c = 0;
+  auto draw = [&]() { return (uint64_t)(((unsigned __int128)splitmix64(seed ^ c++) * n) >> 64); };
+  for (size_t it = 0; it < iterations; ++it) {
+    const uint64_t r1 = draw();
+    uint64_t r2 = draw();
+    while (r1 == r2) r2 = draw();  // segmentation.rs:52-54, :85-87
+    out[it * per] = r1;
+    out[it * per + 1] = r2;
+    if (per == 3) {
+      uint64_t r3 = draw();
+      while (r2 == r3 || r1 == r3) r3 = draw();  // :57-59
+      out[it * per + 2] = r3;
+    }
+  }
+}
+
+struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };
+
+// view_attribute::<Vector3<f64>>(&POSITION_3D): name AND datatype (buffer_views.rs:301-310)
+const Member* position_member(const pst_buffer& b) {
+  DataType v3;
+  v3.kind = PST_VEC3F64;
+  const int slot = b.layout.index_of(AttributeDef{"Position3D", v3});
+  if (slot < 0) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute Position3D (Vec3f64) not found in PointLayout of buffer");
+  return &b.layout.members[(size_t)slot];
+}
+PosView position_view(const pst_buffer& b, const Member* m) {
+  const size_t slot = (size_t)(m - b.layout.members.data());
+  if (b.len >= 0xFFFFFFFFull) throw Error(PST_ERR_UNSUPPORTED, "ransac: 2^32 - 1 points and more per call are not supported");
+  PosView v;
+  v.base = b.len == 0 ? nullptr : (const uint8_t*)(uintptr_t)(b.columnar ? col_addr(b, slot, 0) : aos_addr(b, 0) + m->offset);
+  v.stride = b.columnar ? m->size : b.layout.size;
+  v.n = b.len;
+  return v;
+}
+
+struct Scratch {
+  pstk::DevBuf buf;
+  void* get(size_t bytes, hipStream_t s) {
+    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure("ransac: scratch allocation failed: ");
+    return buf.p;
+  }
+};
+
+struct FitResult { uint64_t best, ranking; double model[6]; };
+
+// checks shared by *_fit and the seeded entry points, in the order the header documents
+PosView fit_checks(const pst_buffer* b, size_t iterations, bool line) {
+  not_null(b, "buffer");
+  if (iterations == 0)  // the reference unwraps the max_by of an empty iterator
+    throw Error(PST_ERR_INVALID_ARGUMENT, "called `Option::unwrap()` on a `None` value (num_of_iterations is 0)");
+  if (iterations > 0xFFFFFFFFull) throw Error(PST_ERR_UNSUPPORTED, "ransac: 2^32 iterations and more are not supported");
+  const Member* m = position_member(*b);
+  ensure_device();
+  const size_t need = line ? 2 : 3;
+  if (b->len < need)
+    throw Error(PST_ERR_TOO_FEW_POINTS, line ? "buffer needs to include at least 2 points to generate a line model."
+                                             : "buffer needs to include at least 3 points to generate a plane model.");
+  return position_view(*b, m);
+}
+
+FitResult fit(const PosView& pv, bool line, double thr, const uint64_t* samples, size_t iterations, uint64_t* rankings) {
+  const size_t per = line ? 2 : 3;
+  for (size_t it = 0; it < iterations; ++it) {
+    const uint64_t* s = samples + it * per;
+    for (size_t k = 0; k < per; ++k)
+      if (s[k] >= pv.n) throw Error(PST_ERR_RANGE, "ransac: sample index " + std::to_string(s[k]) + " out of range for " + std::to_string(pv.n) + " points");
+    if (s[0] == s[1] || (per == 3 && (s[0] == s[2] || s[1] == s[2])))
+      throw Error(PST_ERR_INVALID_ARGUMENT, "ransac: hypothesis " + std::to_string(it) + " repeats a point index (the reference redraws until they differ)");
+  }
+  hipStream_t s = current_stream();
+  const size_t rec_bytes = pstk::ransac_record_bytes(line);
+  // one block of scratch: samples | records | rankings | result record
+  const size_t off_recs = (iterations * per * sizeof(uint64_t) + 255) & ~(size_t)255;
+  const size_t off_rank = off_recs + ((iterations * rec_bytes + 255) & ~(size_t)255);
+  const size_t off_out = off_rank + ((iterations * sizeof(uint64_t) + 255) & ~(size_t)255);
+  Scratch scratch;
+  uint8_t* base = (uint8_t*)scratch.get(off_out + 64, s);
+  PST_HIP_CHECK(hipMemcpyAsync(base, samples, iterations * per * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (!pstk::ransac_fit(line, pv.base, pv.stride, pv.n, thr, (const uint64_t*)base, iterations, base + off_recs, (unsigned long long*)(base + off_rank),
+                        (unsigned long long*)(base + off_out), s))
+    throw hip_failure("ransac launch failed: ");
+  FitResult r{};
+  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_out, sizeof(r), hipMemcpyDeviceToHost, s));
+  if (rankings) PST_HIP_CHECK(hipMemcpyAsync(rankings, base + off_rank, iterations * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  return r;
+}
+
+int fit_entry(const pst_buffer* b, bool line, double thr, const uint64_t* samples, size_t iterations, double* model, uint64_t* ranking, size_t* best_iteration,
+              uint64_t* rankings) {
+  PST_API_BEGIN
+  not_null(samples, "samples");
+  not_null(model, line ? "line" : "plane");
+  not_null(ranking, "ranking");
+  const PosView pv = fit_checks(b, iterations, line);
+  const FitResult r = fit(pv, line, thr, samples, iterations, rankings);
+  std::memcpy(model, r.model, (line ? 6 : 4) * sizeof(double));
+  *ranking = r.ranking;
+  if (best_iteration) *best_iteration = (size_t)r.best;
+  PST_API_END
+}
+
+int seeded_entry(const pst_buffer* b, bool line, double thr, size_t iterations, uint64_t seed, double* model, uint64_t* ranking) {
+  PST_API_BEGIN
+  not_null(model, line ? "line" : "plane");
+  not_null(ranking, "ranking");
+  const PosView pv = fit_checks(b, iterations, line);
+  const size_t per = line ? 2 : 3;
+  std::vector<uint64_t> samples(iterations * per);
+  sample_indices(seed, pv.n, iterations, (uint32_t)per, samples.data());
+  const FitResult r = fit(pv, line, thr, samples.data(), iterations, nullptr);
+  std::memcpy(model, r.model, (line ? 6 : 4) * sizeof(double));
+  *ranking = r.ranking;
+  PST_API_END
+}
+
+int mask_entry(const pst_buffer* b, bool line, const double* model, double thr, uint8_t* device_mask) {
+  PST_API_BEGIN
+  not_null(b, "buffer");
+  not_null(model, line ? "line" : "plane");
+  const Member* m = position_member(*b);
+  if (b->len == 0) return PST_OK;
+  not_null(device_mask, "device_mask");
+  ensure_device();
+  const PosView pv = position_view(*b, m);
+  hipStream_t s = current_stream();
+  Scratch rec;  // released in stream order behind the mask kernel
+  if (!pstk::ransac_mask(line, pv.base, pv.stride, pv.n, model, thr, rec.get(pstk::ransac_record_bytes(line), s), device_mask, s))
+    throw hip_failure("ransac mask launch failed: ");
+  PST_API_END
+}
+
+int inliers_entry(const pst_buffer* b, bool line, const double* model, double thr, uint64_t* indices, size_t capacity, uint64_t* count) {
+  PST_API_BEGIN
+  not_null(b, "buffer");
+  not_null(model, line ? "line" : "plane");
+  not_null(count, "count");
+  const Member* m = position_member(*b);
+  *count = 0;
+  if (b->len == 0) return PST_OK;
+  ensure_device();
+  const PosView pv = position_view(*b, m);
+  hipStream_t s = current_stream();
+  const size_t blocks = (pv.n + pstk::kRansacPointsPerBlock - 1) / pstk::kRansacPointsPerBlock;
+  // counts[blocks + 1] (the last one zero, so that the scan's last offset is the total) | offsets[blocks + 1] | record | scan scratch
+  size_t scan_bytes = 0;
+  if (pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, blocks + 1, s) != hipSuccess) throw hip_failure("ransac: scan sizing failed: ");
+  const size_t off_offsets = ((blocks + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t off_rec = off_offsets + (((blocks + 1) * sizeof(uint64_t) + 255) & ~(size_t)255);
+  const size_t off_scan = off_rec + 256;
+  Scratch scratch;
+  uint8_t* base = (uint8_t*)scratch.get(off_scan + scan_bytes, s);
+  uint32_t* counts = (uint32_t*)base;
+  unsigned long long* offsets = (unsigned long long*)(base + off_offsets);
+  PST_HIP_CHECK(hipMemsetAsync(counts + blocks, 0, sizeof(uint32_t), s));
+  if (!pstk::ransac_model_record(line, model, thr, base + off_rec, s) ||
+      !pstk::ransac_index_pass(line, pv.base, pv.stride, pv.n, base + off_rec, counts, offsets, nullptr, false, s))
+    throw hip_failure("ransac inlier count launch failed: ");
+  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(base + off_scan, scan_bytes, counts, offsets, blocks + 1, s));
+  unsigned long long total = 0;
+  PST_HIP_CHECK(hipMemcpyAsync(&total, offsets + blocks, sizeof(total), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  *count = total;
+  if (!indices) return PST_OK;
+  if (total > capacity)
+    throw Error(PST_ERR_RANGE, "ransac: " + std::to_string(total) + " inliers do not fit the index array of " + std::to_string(capacity));
+  if (total == 0) return PST_OK;
+  Scratch out;
+  unsigned long long* idx_dev = (unsigned long long*)out.get((size_t)total * sizeof(uint64_t), s);
+  if (!pstk::ransac_index_pass(line, pv.base, pv.stride, pv.n, base + off_rec, counts, offsets, idx_dev, true, s))
+    throw hip_failure("ransac inlier index launch failed: ");
+  PST_HIP_CHECK(hipMemcpyAsync(indices, idx_dev, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  PST_API_END
+}
+
+}  // namespace
+
+extern "C" {
+
+int pst_ransac_sample_indices(uint64_t seed, size_t n_points, size_t iterations, uint32_t per_hypothesis, uint64_t* out_indices) {
+  PST_API_BEGIN
+  if (per_hypothesis != 2 && per_hypothesis != 3) throw Error(PST_ERR_INVALID_ARGUMENT, "per_hypothesis must be 3 (plane) or 2 (line)");
+  if (n_points < per_hypothesis)  // the redraw loops would never end
+    throw Error(PST_ERR_TOO_FEW_POINTS, "buffer needs to include at least " + std::to_string(per_hypothesis) + " points to generate a model.");
+  if (iterations == 0) return PST_OK;
+  not_null(out_indices, "out_indices");
+  sample_indices(seed, n_points, iterations, per_hypothesis, out_indices);
+  PST_API_END
+}
+
+int pst_ransac_kernel_shape(uint32_t* points_per_wave, uint32_t* points_per_block, uint32_t* blocks_per_cu, uint32_t* batch) {
+  if (points_per_wave) *points_per_wave = pstk::kRansacPointsPerWave;
+  if (points_per_block) *points_per_block = pstk::kRansacPointsPerBlock;
+  if (blocks_per_cu) *blocks_per_cu = pstk::kRansacBlocksPerCu;
+  if (batch) *batch = pstk::kRansacBatch;
+  return PST_OK;
+}
+
+int pst_ransac_plane_fit(const pst_buffer* b, double distance_threshold, const uint64_t* samples, size_t iterations, double plane[4], uint64_t* ranking,
+                         size_t* best_iteration, uint64_t* rankings) {
+  return fit_entry(b, false, distance_threshold, samples, iterations, plane, ranking, best_iteration, rankings);
+}
+int pst_ransac_line_fit(const pst_buffer* b, double distance_threshold, const uint64_t* samples, size_t iterations, double line[6], uint64_t* ranking,
+                        size_t* best_iteration, uint64_t* rankings) {
+  return fit_entry(b, true, distance_threshold, samples, iterations, line, ranking, best_iteration, rankings);
+}
+int pst_ransac_plane(const pst_buffer* b, double distance_threshold, size_t iterations, uint64_t seed, double plane[4], uint64_t* ranking) {
+  return seeded_entry(b, false, distance_threshold, iterations, seed, plane, ranking);
+}
+int pst_ransac_line(const pst_buffer* b, double distance_threshold, size_t iterations, uint64_t seed, double line[6], uint64_t* ranking) {
+  return seeded_entry(b, true, distance_threshold, iterations, seed, line, ranking);
+}
+int pst_plane_inliers(const pst_buffer* b, const double plane[4], double distance_threshold, uint64_t* indices, size_t capacity, uint64_t* count) {
+  return inliers_entry(b, false, plane, distance_threshold, indices, capacity, count);
+}
+int pst_line_inliers(const pst_buffer* b, const double line[6], double distance_threshold, uint64_t* indices, size_t capacity, uint64_t* count) {
+  return inliers_entry(b, true, line, distance_threshold, indices, capacity, count);
+}
+int pst_plane_inlier_mask_device(const pst_buffer* b, const double plane[4], double distance_threshold, uint8_t* device_mask) {
+  return mask_entry(b, false, plane, distance_threshold, device_mask);
+}
+int pst_line_inlier_mask_device(const pst_buffer* b, const double line[6], double distance_threshold, uint8_t* device_mask) {
+  return mask_entry(b, true, line, distance_threshold, device_mask);
+}
+
+}  // extern "C"

@@ -6,7 +6,7 @@
 //!   DeviceVectorBuffer, DeviceHashMapBuffer         ~ VectorBuffer, HashMapBuffer      (containers/point_buffer.rs), storage in HBM
 //!   PinnedVectorBuffer, PinnedHashMapBuffer         ~ the same with `&[u8]` views: pinned host memory both pasture's CPU code and the kernels address
 //!   DeviceBufferLayoutConverter                     ~ BufferLayoutConverter            (layout/conversion/buffer_conversion.rs)
-//!   calculate_bounds, minmax_attribute, compute_centroid, compute_normals, voxelgrid_filter (pasture-algorithms)
+//!   calculate_bounds, minmax_attribute, compute_centroid, compute_normals, voxelgrid_filter, ransac_plane_serial, ransac_line_serial (pasture-algorithms)
 //!   SliceDeviceBuffer::slice / slice_mut            ~ SliceBuffer / SliceBufferMut     (containers/slice.rs)
 //!   view_attribute_with_conversion                  ~ BorrowedBufferExt::view_attribute_with_conversion (containers/point_buffer.rs:322)
 use pasture_amd_sys::*;
@@ -291,6 +291,32 @@ pub fn compute_normals(buffer: &impl DeviceBuffer, k_nn: usize) -> Vec<(Vector3<
 /// pasture-algorithms/src/voxel_grid.rs:109
 pub fn voxelgrid_filter(buffer: &impl DeviceBuffer, leafsize_x: f64, leafsize_y: f64, leafsize_z: f64, filtered_buffer: &mut impl DeviceBuffer) {
     check(unsafe { pst_voxelgrid_filter(buffer.handle(), leafsize_x, leafsize_y, leafsize_z, filtered_buffer.handle()) })
+}
+
+/// segmentation.rs:19-28 / :10-17 with public fields (the reference's are private and have no accessors)
+#[derive(Debug, Clone, Copy)]
+pub struct Plane { pub a: f64, pub b: f64, pub c: f64, pub d: f64, pub ranking: usize }
+#[derive(Debug, Clone, Copy)]
+pub struct Line { pub first: Vector3<f64>, pub second: Vector3<f64>, pub ranking: usize }
+
+/// pasture-algorithms/src/segmentation.rs:239 (ransac_plane_serial).  The reference draws its hypotheses from rand::thread_rng(); here they come
+/// from the library's seeded sampler (pst_ransac_sample_indices), so a seed is part of the signature.
+pub fn ransac_plane_serial(buffer: &impl DeviceBuffer, distance_threshold: f64, num_of_iterations: usize, seed: u64) -> (Plane, Vec<usize>) {
+    let (mut m, mut ranking) = ([0f64; 4], 0u64);
+    check(unsafe { pst_ransac_plane(buffer.handle(), distance_threshold, num_of_iterations, seed, m.as_mut_ptr(), &mut ranking) });
+    let (mut indices, mut count) = (vec![0u64; ranking as usize], 0u64);
+    check(unsafe { pst_plane_inliers(buffer.handle(), m.as_ptr(), distance_threshold, indices.as_mut_ptr(), indices.len(), &mut count) });
+    (Plane { a: m[0], b: m[1], c: m[2], d: m[3], ranking: ranking as usize }, indices.into_iter().map(|i| i as usize).collect())
+}
+
+/// pasture-algorithms/src/segmentation.rs:353 (ransac_line_serial)
+pub fn ransac_line_serial(buffer: &impl DeviceBuffer, distance_threshold: f64, num_of_iterations: usize, seed: u64) -> (Line, Vec<usize>) {
+    let (mut m, mut ranking) = ([0f64; 6], 0u64);
+    check(unsafe { pst_ransac_line(buffer.handle(), distance_threshold, num_of_iterations, seed, m.as_mut_ptr(), &mut ranking) });
+    let (mut indices, mut count) = (vec![0u64; ranking as usize], 0u64);
+    check(unsafe { pst_line_inliers(buffer.handle(), m.as_ptr(), distance_threshold, indices.as_mut_ptr(), indices.len(), &mut count) });
+    (Line { first: Vector3::new(m[0], m[1], m[2]), second: Vector3::new(m[3], m[4], m[5]), ranking: ranking as usize },
+     indices.into_iter().map(|i| i as usize).collect())
 }
 
 impl DeviceHashMapBuffer {
