@@ -17,14 +17,12 @@ size_t bounds_partials_scratch_bytes(size_t count) { return std::max(pstk::strea
 void bounds_of_range(const pst_buffer& b, size_t first, size_t count, double* out6, hipStream_t stream, void* partials) {
   const Member* pm = b.layout.find_by_name("Position3D");
   if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "buffer has no Position3D attribute");
-  const size_t slot = (size_t)(pm - b.layout.members.data());
   const DataType& dt = pm->def.datatype;
   // non-default position datatypes go through the `as` table (bounds.rs:56-85); impossible pairs panic in
   // get_generic_converter (attribute_conversion.rs:267-269)
   if (dt.kind != PST_VEC3F64 && !position_convertible_to_vec3f64(dt))
     throw Error(PST_ERR_INVALID_CONVERSION, "Invalid conversion " + dt.display() + " -> Vec3<f64>");
-  const uint64_t base = b.columnar ? col_addr(b, slot, first) : aos_addr(b, first) + pm->offset;
-  const uint64_t stride = b.columnar ? pm->size : b.layout.size;
+  const auto [base, stride] = attr_view(b, pm, first);
   if (b.columnar && dt.kind == PST_VEC3F64 && base % 8 == 0) {
     // K1: coalesced 16-byte stream over the column
     pstk::launch_vec3f64_stream((const double*)(uintptr_t)base, nullptr, count, nullptr, nullptr, 4u,
@@ -91,8 +89,7 @@ int pst_minmax_attribute(const pst_buffer* b, const char* name, const pst_dataty
   const Member& m = b->layout.members[(size_t)slot];
   Workspace& ws = workspace();
   hipStream_t s = current_stream();
-  const uint64_t base = b->columnar ? col_addr(*b, (size_t)slot, 0) : aos_addr(*b, 0) + m.offset;
-  const uint64_t stride = b->columnar ? m.size : b->layout.size;
+  const auto [base, stride] = attr_view(*b, (size_t)slot);
   const uint32_t ncomp = def.datatype.num_components();
   const size_t csize = m.size / ncomp;
   uint8_t* dev_rec = ws.dev + Workspace::kWorkspaceBytes - 64;  // 2 * ncomp * csize <= 48 bytes
@@ -128,15 +125,12 @@ int pst_compute_centroid(const pst_buffer* b, double out_centroid[3]) {
   not_null(b, "buffer");
   not_null(out_centroid, "out_centroid");
   if (b->len == 0) throw Error(PST_ERR_TOO_FEW_POINTS, "The point cloud is empty!");
-  DataType v3; v3.kind = PST_VEC3F64;
-  const int slot = b->layout.index_of(AttributeDef{"Position3D", v3});
-  if (slot < 0) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member* m = position_vec3f64(*b);
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
   ensure_device();
-  const Member& m = b->layout.members[(size_t)slot];
   Workspace& ws = workspace();
   hipStream_t s = current_stream();
-  const uint64_t base = b->columnar ? col_addr(*b, (size_t)slot, 0) : aos_addr(*b, 0) + m.offset;
-  const uint64_t stride = b->columnar ? m.size : b->layout.size;
+  const auto [base, stride] = attr_view(*b, m);
   double* partials = (double*)ws.partials(pstk::centroid_partials_bytes());
   const unsigned n_rec = pstk::launch_centroid((const uint8_t*)(uintptr_t)base, stride, b->len, partials, s);
   PST_HIP_CHECK(hipGetLastError());
@@ -197,7 +191,7 @@ int pst_transform_attribute(pst_buffer* b, const char* name, const pst_datatype*
     bool done = false;
     uint64_t attr_bytes = 0;
     for (const Member& mm : b->layout.members) attr_bytes += mm.size;
-    static const bool whole_env = [] { const char* v = std::getenv("PST_TRANSFORM_WHOLE_RECORDS"); return !(v && *v == '0'); }();  // the A/B switch
+    static const bool whole_env = env_on("PST_TRANSFORM_WHOLE_RECORDS");  // the A/B switch
     if (whole_env && attr_bytes == b->layout.size && b->layout.members.size() <= PST_PLAN_MAX_ENTRIES) {
       std::vector<PlanEntry> all;
       for (size_t a = 0; a < b->layout.members.size(); ++a) all.push_back((int)a == slot ? e : identity_entry(b->layout.members[a], b->layout.members[a]));

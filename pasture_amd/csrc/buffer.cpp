@@ -87,7 +87,7 @@ static bool pool_ready() {
   // per device: every GPU has its own default pool, and each needs its release threshold raised once
   static std::mutex mu;
   static int state[64] = {};  // 0 = not asked yet, 1 = ready, 2 = no pool support
-  if (std::getenv("PST_NO_POOL")) return false;
+  if (env_str("PST_NO_POOL")) return false;  // (set at all; read per call)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
   std::lock_guard<std::mutex> lock(mu);
@@ -356,7 +356,7 @@ int pst_buffer_create(const pst_layout* l, uint32_t storage, uint32_t memkind, p
 // PST_EXTERNAL_UNCHECKED=1 skips the question (memory of another runtime that HIP cannot describe but the device can reach).
 // Returns PST_MEM_PINNED_HOST for host memory the device maps, PST_MEM_DEVICE otherwise.
 static uint32_t check_device_reaches(const void* p, size_t nbytes, const char* what) {
-  static const bool unchecked = [] { const char* v = std::getenv("PST_EXTERNAL_UNCHECKED"); return v && *v == '1'; }();
+  static const bool unchecked = [] { const char* v = env_str("PST_EXTERNAL_UNCHECKED"); return v && *v == '1'; }();
   if (!nbytes || unchecked) return PST_MEM_DEVICE;
   ensure_device();
   uint32_t kind = PST_MEM_DEVICE;
@@ -581,8 +581,9 @@ int pst_buffer_synth_fill(pst_buffer* b, uint64_t seed, uint64_t first_index) {
   for (size_t a = 0; a < b->layout.members.size(); ++a) {
     const Member& m = b->layout.members[a];
     pstk::SynthAttr sa{};
-    sa.base = b->columnar ? (uint64_t)(uintptr_t)b->columns[a] : (uint64_t)(uintptr_t)b->data + m.offset;
-    sa.stride = b->columnar ? m.size : b->layout.size;
+    const AttrView v = attr_view(*b, a);
+    sa.base = v.addr;
+    sa.stride = v.stride;
     sa.size = (uint32_t)m.size;
     sa.slot = (uint32_t)a;
     sa.kind = m.def.datatype.kind;

@@ -18,6 +18,7 @@
 //
 // HBM-bound integer/byte work: no MFMA.  Compiled with -ffp-contract=off (affine = two roundings).
 #include "convert_kernels.hpp"
+#include "env.hpp"
 #include "jit.hpp"
 
 #include <cstdio>
@@ -49,11 +50,6 @@ int device_cus() {
   if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
   by_device[dev] = n;
   return n;
-}
-
-static long env_long(const char* name, long dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::strtol(v, nullptr, 10) : dflt;
 }
 
 // Plan entries are uploaded into a small ring of device slots; hipMemcpyAsync from pageable host memory stages the
@@ -94,7 +90,7 @@ unsigned convert_grid(const ConvertPlan& plan, bool src_aos, bool dst_aos, bool 
   if (use_lds && (src_aos || dst_aos)) {
     const uint64_t n_tiles = (h.n + h.tile - 1) / h.tile;
     // one tile per block: staggered blocks keep HBM reads and writes interleaved (see stream.hip); cap for huge inputs
-    static const long cap = env_long("PST_TILE_GRID_CAP", 1 << 22);
+    static const long cap = pst::env_long("PST_TILE_GRID_CAP", 1 << 22);
     return (unsigned)((std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, (uint64_t)cap)) + 7) / 8 * 8);  // multiple of 8: xcd_block_id()
   }
   uint64_t max_comp = 1;
@@ -116,7 +112,7 @@ void reset_plan_kinds() { t_plan_kinds = 0; }
 void note_plan_kind(uint32_t kind) { t_plan_kinds |= 1u << kind; }
 uint32_t plan_kinds() { return t_plan_kinds; }
 void note_slow_family(const char* what, uint64_t n_points, const char* why) {
-  static const bool quiet = [] { const char* v = std::getenv("PST_QUIET"); return v && *v && *v != '0'; }();
+  static const bool quiet = pst::env_nonzero("PST_QUIET");
   if (quiet || n_points < ((uint64_t)1 << 20)) return;
   static std::mutex mu;
   static std::set<std::string> seen;

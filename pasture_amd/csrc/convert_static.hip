@@ -7,6 +7,7 @@
 #include <cstring>
 #include <string>
 
+#include "env.hpp"
 #include "jit_quad.hpp"
 #include "kernels.hpp"
 
@@ -35,7 +36,7 @@ namespace pstk {
 // returns true; false when no in-tree plan has that text.  tile_only: just report the tile.
 bool launch_convert_static(const std::string& source, uint32_t* tile, bool tile_only, unsigned grid, const ConvertHeader& h, const PlanEntry* entries,
                            hipStream_t stream) {
-  static const bool enabled = [] { const char* v = std::getenv("PST_STATIC_PLANS"); return !(v && *v == '0'); }();
+  static const bool enabled = pst::env_on("PST_STATIC_PLANS");
   if (!enabled) return false;
 #define PST_TRY_PLAN(NAME)                                             \
   if (source == k##NAME##Source) {                                     \

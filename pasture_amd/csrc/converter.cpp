@@ -110,13 +110,18 @@ static PlanEntry entry_from_mapping(const Mapping& m) {
   return e;
 }
 
+// the A/B switches this file asks for in more than one place
+static bool expr_fuse_enabled() { static const bool on = env_on("PST_EXPR_FUSE"); return on; }
+static bool las_decode_enabled() { static const bool on = env_on("PST_LAS_DECODE"); return on; }
+static bool las_prefer_specialised() { static const bool on = env_on("PST_LAS_PREFER_SPECIALISED"); return on; }
+
 // LDS tile: ~36 KiB of records per block (4 resident blocks per CU; measured best on MI355X: larger tiles amortise the
 // per-entry interpretation cost, smaller ones raise occupancy), multiple of 64 points.  PST_TILE_POINTS overrides (tuning).
 static uint32_t pick_tile(bool src_aos, uint32_t src_stride, bool dst_aos, uint32_t dst_stride) {
   const uint64_t per_point = (src_aos ? src_stride : 0) + (dst_aos ? dst_stride : 0);
   if (per_point == 0) return 0;
-  static const long forced = [] { const char* v = std::getenv("PST_TILE_POINTS"); return v && *v ? std::strtol(v, nullptr, 10) : 0L; }();
-  static const long budget_env = [] { const char* v = std::getenv("PST_TILE_LDS_BYTES"); return v && *v ? std::strtol(v, nullptr, 10) : 0L; }();
+  static const long forced = env_long("PST_TILE_POINTS", 0);
+  static const long budget_env = env_long("PST_TILE_LDS_BYTES", 0);
   const uint64_t hard_cap = 160 * 1024 - 256;
   uint64_t t;
   if (forced > 0) {
@@ -147,7 +152,7 @@ static ConvertPlan build_plan(bool src_aos, uint64_t src_base, uint32_t src_stri
   // Four points per lane put the lanes of a wave `stride` DWORDS apart in the record tile: strides that are multiples of 32 bytes
   // pile them onto the same LDS banks (measured 32 B: 5.96 -> 4.55 TB/s), every other stride gains (41 B: 4.20 -> 5.87).
   // PST_TILE_QUAD=0 / 1 forces the mapping (tuning).
-  static const int quad_env = [] { const char* v = std::getenv("PST_TILE_QUAD"); return v && *v ? (*v == '0' ? 0 : 1) : -1; }();
+  static const int quad_env = [] { const char* v = env_str("PST_TILE_QUAD"); return v && *v ? (*v == '0' ? 0 : 1) : -1; }();
   plan.h.quad = quad_env >= 0 ? (uint32_t)quad_env : ((dst_stride % 32u != 0 && !(src_aos && src_stride % 32u == 0)) ? 1u : 0u);
   std::vector<uint8_t> covered(dst_aos ? dst_stride : 0, 0);
   *wants_bounds = false;
@@ -162,7 +167,7 @@ static ConvertPlan build_plan(bool src_aos, uint64_t src_base, uint32_t src_stri
   // wave scheduling of the tile kernels (convert.hip): narrow attributes are owned by single waves, balanced by bytes
   {
     const long nwaves = 4;  // convert_tile_kernel runs 256-thread blocks
-    static const long own_max = [] { const char* v = std::getenv("PST_TILE_OWN_MAX_BYTES"); return v && *v ? std::strtol(v, nullptr, 10) : 4L; }();
+    static const long own_max = env_long("PST_TILE_OWN_MAX_BYTES", 4);
     uint64_t load[16] = {0};
     for (size_t i = 0; i < cnt; ++i) {
       const uint32_t col_bytes = (src_aos && !dst_aos) ? plan.e[i].dst_size : (!src_aos && dst_aos) ? plan.e[i].src_size
@@ -225,10 +230,9 @@ void execute_entries(bool src_aos, uint64_t src_base, uint32_t src_stride, bool 
 // point's index, p[0 .. 3] the arrays it names.  Returns the points covered (full tiles; 0: no such kernel for this layout / PST_JIT=0 -- the caller's
 // strided kernel takes everything); throws when the kernel with the expression in it does not compile.
 uint64_t transform_records_with_expression(const pst_buffer& b, int slot, const std::string& expr, const double* const p[4], hipStream_t stream) {
-  static const bool fuse_env = [] { const char* v = std::getenv("PST_EXPR_FUSE"); return !(v && *v == '0'); }();
   uint64_t attr_bytes = 0;
   for (const Member& mm : b.layout.members) attr_bytes += mm.size;
-  if (!fuse_env || b.columnar || b.len == 0 || attr_bytes != b.layout.size || b.layout.members.size() > PST_PLAN_MAX_ENTRIES || pstjit::mode() == pstjit::Mode::Off) return 0;
+  if (!expr_fuse_enabled() || b.columnar || b.len == 0 || attr_bytes != b.layout.size || b.layout.members.size() > PST_PLAN_MAX_ENTRIES || pstjit::mode() == pstjit::Mode::Off) return 0;
   std::vector<PlanEntry> all;
   for (size_t a = 0; a < b.layout.members.size(); ++a) {
     PlanEntry e = identity_entry(b.layout.members[a], b.layout.members[a]);
@@ -280,8 +284,7 @@ static std::vector<PlanEntry> interleaved_source_entries(const pst_converter& c,
 // force_family: -1 = by the converter's measured choice (default: plan-specialised), 0 = the LAS family, 1 = plan-specialised if at hand
 static bool las_plan_prefers_generic(const pst_converter& c, const pst_buffer& src, size_t s0, const pst_buffer& dst, size_t t0, uint64_t n, int pos_slot,
                                      bool with_bounds, int force_family) {
-  static const bool on = [] { const char* v = std::getenv("PST_LAS_PREFER_SPECIALISED"); return !(v && *v == '0'); }();  // the A/B switch
-  if (!on || force_family == 0) return false;
+  if (!las_prefer_specialised() || force_family == 0) return false;
   const int choice = c.family_choice[family_slot(src.columnar, dst.columnar)][with_bounds ? 1 : 0];
   if (force_family < 0 && choice == 0) return false;
   if (src.columnar) {
@@ -388,7 +391,7 @@ static bool storage_overlaps(const pst_buffer& src, size_t s0, size_t s1, const 
 // stream is being captured into a graph, below 2^22 points, when source and target memory overlap, and when the plan-specialised kernel is not
 // compiled yet.  PST_FAMILY_AUTOTUNE=0 switches it off (the default order of preference then stands: plan-specialised first).
 static void family_autotune(const pst_converter& c, pst_buffer& src, size_t s0, size_t s1, pst_buffer& dst, size_t t0, size_t t1, double* bounds_out6, hipStream_t stream) {
-  static const bool on = [] { const char* v = std::getenv("PST_FAMILY_AUTOTUNE"); return !(v && *v == '0'); }();
+  static const bool on = env_on("PST_FAMILY_AUTOTUNE");
   const uint64_t n = s1 - s0;
   const int slot = family_slot(src.columnar, dst.columnar), bslot = bounds_out6 ? 1 : 0;
   std::atomic<int>& choice = c.family_choice[slot][bslot];
@@ -460,9 +463,8 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     pos_slot = (int)(pm - c.to.members.data());
   }
   // where the target's positions are: the last fold gives a +-0 bound the sign of the first zero there (zero_sign.hpp)
-  const pstk::ZeroScan folded = bounds_out6 ? pstk::ZeroScan{dst.columnar ? col_addr(dst, (size_t)pos_slot, t0) : aos_addr(dst, t0) + c.to.members[(size_t)pos_slot].offset,
-                                                             dst.columnar ? c.to.members[(size_t)pos_slot].size : c.to.size, n}
-                                            : pstk::ZeroScan{0, 0, 0};
+  const AttrView pos_view = bounds_out6 ? attr_view(dst, (size_t)pos_slot, t0) : AttrView{0, 0};
+  const pstk::ZeroScan folded{pos_view.addr, pos_view.stride, bounds_out6 ? n : 0};
   bool bounds_done = false;
 
   if (n > 0 && !src.columnar && !dst.columnar && !bounds_out6) {
@@ -479,8 +481,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
       return;
     }
   }
-  static const bool las_fast = [] { const char* v = std::getenv("PST_LAS_DECODE"); return !(v && *v == '0'); }();
-  if (las_fast && n > 0 && src.columnar != dst.columnar) {
+  if (las_decode_enabled() && n > 0 && src.columnar != dst.columnar) {
     if (c.las_typed_format == -2) {
       c.las_typed_format = -1;
       if (match_identity_records(c))
@@ -504,8 +505,8 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     }
   }
   std::vector<PlanEntry> generic;
-  if (las_fast && n > 0 && !src.columnar && c.las_decode_format == -2) c.las_decode_format = match_las_decode_plan(c);
-  if (las_fast && n > 0 && !src.columnar && c.las_decode_format >= 0 &&
+  if (las_decode_enabled() && n > 0 && !src.columnar && c.las_decode_format == -2) c.las_decode_format = match_las_decode_plan(c);
+  if (las_decode_enabled() && n > 0 && !src.columnar && c.las_decode_format >= 0 &&
       !(!dst.columnar && las_plan_prefers_generic(c, src, s0, dst, t0, n, pos_slot, bounds_out6 != nullptr, force_family))) {
     // the production plan of the LAS readers: format-specialised kernel (las_decode.hip)
     const Mapping* pos = nullptr;
@@ -541,8 +542,7 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
     // expression mapping, the index the expression sees is the point's index in the SOURCE buffer either way.
     bool any_expr = false;
     for (const Mapping& m : c.mappings) any_expr = any_expr || !m.expr.empty();
-    static const bool fuse_env = [] { const char* v = std::getenv("PST_EXPR_FUSE"); return !(v && *v == '0'); }();  // the A/B switch
-    const bool fuse_expr = any_expr && fuse_env && !(src.columnar && dst.columnar) && c.mappings.size() <= PST_PLAN_MAX_ENTRIES && pstjit::mode() != pstjit::Mode::Off;
+    const bool fuse_expr = any_expr && expr_fuse_enabled() && !(src.columnar && dst.columnar) && c.mappings.size() <= PST_PLAN_MAX_ENTRIES && pstjit::mode() != pstjit::Mode::Off;
     struct ExprPass { const Mapping* m; uint64_t src, sstride, dst, dstride; };
     std::vector<ExprPass> expr_passes;
     std::vector<std::string> expr_texts;
@@ -557,8 +557,8 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
       if (src.columnar) e.src_col = col_addr(src, (size_t)sslot, s0);
       if (dst.columnar) e.dst_col = col_addr(dst, (size_t)tslot, t0);
       if (!m.expr.empty()) {
-        const ExprPass x{&m, src.columnar ? e.src_col : aos_addr(src, s0) + m.source.offset, src.columnar ? m.source.size : c.from.size,
-                         dst.columnar ? e.dst_col : aos_addr(dst, t0) + m.target.offset, dst.columnar ? m.target.size : c.to.size};
+        const AttrView sv = attr_view(src, (size_t)sslot, s0), tv = attr_view(dst, (size_t)tslot, t0);
+        const ExprPass x{&m, sv.addr, sv.stride, tv.addr, tv.stride};
         if (fuse_expr) {
           e.xf_kind = (uint8_t)PST_XF_EXPR;
           e.xf_on_source = m.apply_to_source ? 1 : 0;
@@ -652,17 +652,15 @@ static void convert_range(const pst_converter& c, pst_buffer& src, size_t s0, si
 // (only their equality pattern matters to the specialised kernels): what pst_converter_prepare compiles ahead of the first call.
 // Returns the PST_PLAN_* family the call would take WITHOUT a specialised kernel, and fills `plan` when that family is the generic one.
 static uint32_t plan_for_storage(const pst_converter& c, bool src_columnar, bool dst_columnar, bool with_bounds, ConvertPlan* plan, std::vector<std::string>* expr_texts) {
-  static const bool las_fast = [] { const char* v = std::getenv("PST_LAS_DECODE"); return !(v && *v == '0'); }();
   if (c.mappings.empty()) return PST_PLAN_NONE;
   if (!src_columnar && !dst_columnar && !with_bounds && match_identity_records(c)) return PST_PLAN_COPY;
   // (typed LAS records -> columns and raw LAS records -> typed records prefer a plan-specialised kernel when the run-time compiler is on:
   //  las_plan_prefers_generic above; pst_converter_prepare then compiles the generic plan, and the LAS kernel stays the stand-in)
-  static const bool prefer_generic = [] { const char* v = std::getenv("PST_LAS_PREFER_SPECIALISED"); return !(v && *v == '0'); }();
-  const bool jit_on = prefer_generic && pstjit::mode() != pstjit::Mode::Off;
-  if (las_fast && src_columnar != dst_columnar && match_identity_records(c) && !jit_on)  // (with the compiler on: the generic plan is compiled for BOTH directions, family_autotune picks)
+  const bool jit_on = las_prefer_specialised() && pstjit::mode() != pstjit::Mode::Off;
+  if (las_decode_enabled() && src_columnar != dst_columnar && match_identity_records(c) && !jit_on)  // (with the compiler on: the generic plan is compiled for BOTH directions, family_autotune picks)
     for (uint32_t f = 0; f <= 10; ++f)
       if (c.to == laslayout::typed_layout(f)) return PST_PLAN_LAS;
-  if (las_fast && !src_columnar && match_las_decode_plan(c) >= 0 && !(jit_on && !dst_columnar)) return PST_PLAN_LAS;
+  if (las_decode_enabled() && !src_columnar && match_las_decode_plan(c) >= 0 && !(jit_on && !dst_columnar)) return PST_PLAN_LAS;
   if (src_columnar && dst_columnar) return PST_PLAN_COLUMN;
   bool any_expr = false;
   for (const Mapping& m : c.mappings) any_expr = any_expr || !m.expr.empty();

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/pasture_amd.h"
+#include "env.hpp"
 
 namespace pst {
 

@@ -3,11 +3,12 @@
 #include <cstdlib>
 
 #include "device_sort.hpp"
+#include "env.hpp"
 
 namespace pstk {
 
 RadixFirstPass sort_first_pass(void* tmp, size_t n, unsigned end_bit) {
-  static const bool no_fuse = [] { const char* e = std::getenv("PST_SORT_FUSE"); return e && *e == '0'; }();  // A/B: the sort counts its first histogram itself
+  static const bool no_fuse = !pst::env_on("PST_SORT_FUSE");  // A/B: the sort counts its first histogram itself
   if (no_fuse || !radix_sort_pairs_supported(n, end_bit) || !tmp || n == 0) return RadixFirstPass{nullptr, 0, 0, 0};
   return radix_sort_first_pass(tmp, n, end_bit);
 }

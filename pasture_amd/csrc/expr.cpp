@@ -383,9 +383,7 @@ int pst_transform_attribute_expr(pst_buffer* b, const char* name, const pst_data
   ensure_device();
   hipStream_t st = current_stream();
   pstk::reset_plan_kinds();
-  const Member& m = b->layout.members[(size_t)slot];
-  const uint64_t base = b->columnar ? col_addr(*b, (size_t)slot, 0) : aos_addr(*b, 0) + m.offset;
-  const uint64_t stride = b->columnar ? m.size : b->layout.size;
+  const auto [base, stride] = attr_view(*b, (size_t)slot);
   // interleaved records without padding: the whole tiles through the plan-specialised kernel with the expression inside (one pass over the
   // records instead of a strided read-modify-write of one attribute); the ragged rest -- or everything -- through the expression's own kernel
   const uint64_t done = transform_records_with_expression(*b, slot, s.expr, p, st);
@@ -407,9 +405,9 @@ int pst_buffer_filter_expr(const pst_buffer* src, const char* expr, const double
   std::vector<pstexpr::PredAttr> attrs = pstexpr::referenced_attributes(src->layout, expr);
   for (pstexpr::PredAttr& a : attrs) {
     const Member* m = src->layout.find_by_name(a.name);
-    const size_t slot = (size_t)(m - src->layout.members.data());
-    a.base = col_addr(*src, slot, 0);
-    a.stride = m->size;
+    const AttrView v = attr_view(*src, m);  // (columnar: checked above)
+    a.base = v.addr;
+    a.stride = v.stride;
   }
   const double* p[4];
   pstexpr::fill_params(device_params, n_params, p);
@@ -420,7 +418,7 @@ int pst_buffer_filter_expr(const pst_buffer* src, const char* expr, const double
   // layout takes the streaming compaction kernel (filter_stream.hpp: points of at most 64 / 96 bytes), the count pass evaluates the predicate on the
   // columns it names and the scatter pass evaluates it again on the values it holds in registers: no byte mask is written or read, one launch
   // less.  Everything else -- wider points, PST_JIT constraints, PST_EXPR_FUSE=0 (the A/B switch) -- keeps the mask.
-  static const bool fuse_env = [] { const char* v = std::getenv("PST_EXPR_FUSE"); return !(v && *v == '0'); }();
+  static const bool fuse_env = env_on("PST_EXPR_FUSE");
   const size_t na = src->layout.members.size();
   std::vector<uint32_t> sizes(na);
   size_t covered_bytes = 0;
@@ -461,7 +459,7 @@ int pst_buffer_filter_expr(const pst_buffer* src, const char* expr, const double
         const Member& m = src->layout.members[a];
         src_addr[a] = col_addr(*src, a, 0);
         src_stride[a] = (uint32_t)m.size;
-        dst_addr[a] = b->columnar ? col_addr(*b, a, 0) : 0;
+        dst_addr[a] = b->columnar ? col_addr(*b, a, 0) : 0;  // interleaved target: the records' base and dst_off instead
         dst_off[a] = (uint32_t)m.offset;
       }
       // the ragged last tile (less than 2048 points) goes through the gather kernel, which reads a mask: its bytes only

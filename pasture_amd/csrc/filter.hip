@@ -17,6 +17,7 @@
 //                         targets through an LDS record tile and 16-byte stores.
 // HBM-bound gather/scatter: no MFMA.
 #include "device_common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 #include "las_device.hpp"
 #include "tile_io.hpp"
@@ -558,7 +559,7 @@ static bool stream_sig_from_args(const FilterArgs& a, bool dst_aos, StreamSig* s
   }
   // bytes per point: 64 into columns (typed LAS-9, 75 bytes in 18 spans: 0.36 of peak against the gather kernel's 0.58 -- the span bookkeeping
   // spills), 96 into records (LAS-9 0.43 -> 0.66, LAS-5 0.44 -> 0.67: every LAS point format fits); PST_FILTER_STREAM_MAX_BYTES overrides both
-  static const uint32_t max_env = [] { const char* v = std::getenv("PST_FILTER_STREAM_MAX_BYTES"); return v && *v ? (uint32_t)std::atoi(v) : 0u; }();
+  static const uint32_t max_env = (uint32_t)(int)pst::env_long("PST_FILTER_STREAM_MAX_BYTES", 0);
   if (total > (max_env ? max_env : dst_aos ? 96u : 64u)) return false;
   // records whose every byte is written are assembled as images; records with padding (or with attributes the source lacks) are staged from
   // the target and only the attributes' bytes replaced
@@ -666,6 +667,10 @@ __global__ __launch_bounds__(pstf::kStreamThreads) __attribute__((amdgpu_waves_p
   pstf::filter_stream_body<P, 2>(a);
 }
 
+// the A/B switches this file asks for in more than one place
+static bool filter_stream_enabled() { static const bool on = pst::env_on("PST_FILTER_STREAM"); return on; }
+static bool static_plans_enabled() { static const bool on = pst::env_on("PST_STATIC_PLANS"); return on; }
+
 template <typename P>
 static bool stream_sig_is(const StreamSig& s) {
   if (s.n != P::n || s.dst_columns != P::dst_columns || s.covered != P::covered || s.dst_stride != P::dst_stride || s.cap != P::cap) return false;
@@ -676,7 +681,7 @@ static bool stream_sig_is(const StreamSig& s) {
 template <typename P>
 static void launch_stream_static(unsigned grid, hipStream_t stream, const FilterArgs& a) {
   const uint32_t lds = pstk::lds_with_resident_cap(pstf::stream_lds_bytes<P>(), pstk::kResidentFilterStream);
-  static const bool three = [] { const char* v = std::getenv("PST_FILTER_THREE_BLOCKS"); return !(v && *v == '0'); }();  // (0: the A/B switch)
+  static const bool three = pst::env_on("PST_FILTER_THREE_BLOCKS");  // (0: the A/B switch)
   auto kfn = filter_stream_static_kernel<P>;
   if constexpr (StreamOccupancy<P>::three_blocks) {
     if (three) kfn = filter_stream_static3_kernel<P>;
@@ -688,8 +693,7 @@ static void launch_stream_static(unsigned grid, hipStream_t stream, const Filter
 // covered (0: none -- the caller takes the gather kernel for everything) and the plan family.
 static uint32_t launch_stream_tiles(const FilterArgs& a, bool dst_aos, hipStream_t stream, uint32_t* kind, const pstk::FilterPredicate* pred = nullptr,
                                     std::string* error = nullptr) {
-  static const bool enabled = [] { const char* v = std::getenv("PST_FILTER_STREAM"); return !(v && *v == '0'); }();
-  static const bool in_tree = [] { const char* v = std::getenv("PST_STATIC_PLANS"); return !(v && *v == '0'); }();
+  const bool enabled = filter_stream_enabled(), in_tree = static_plans_enabled();
   const uint64_t n_full = a.n / pstf::kStreamTile;
   StreamSig sig;
   const pstjit::Mode mode = pstjit::mode();
@@ -744,7 +748,7 @@ uint32_t filter_tile(bool, uint32_t) { return 2048; }
 // 16 KiB 4.60, 21 KiB 4.43, 32 KiB 3.76 TB/s; 15 KiB + the 4 KiB index list leave room for eight blocks per CU, which the kernel's
 // register budget -- amdgpu_waves_per_eu(8) -- matches: +3 %), a multiple of 16.  PST_FILTER_TILE_LDS overrides the byte budget (tuning).
 static uint32_t filter_chunk(uint32_t dst_stride, long default_budget = 15L * 1024L) {
-  static const long forced = [] { const char* v = std::getenv("PST_FILTER_TILE_LDS"); return v && *v ? std::strtol(v, nullptr, 10) : 0L; }();
+  static const long forced = pst::env_long("PST_FILTER_TILE_LDS", 0);
   const long budget = forced > 0 ? forced : default_budget;
   uint64_t c = (uint64_t)budget / (dst_stride ? dst_stride : 1u);
   c = c / 16 * 16;
@@ -792,9 +796,8 @@ static bool synthetic_stream_sig(const uint32_t* size, int n_attrs, bool dst_aos
   return stream_sig_from_args(a, dst_aos, sig);
 }
 bool filter_predicate_streams(const uint32_t* size, int n_attrs, bool dst_aos, uint32_t dst_stride, bool dst_covered) {
-  static const bool enabled = [] { const char* v = std::getenv("PST_FILTER_STREAM"); return !(v && *v == '0'); }();
   StreamSig sig;
-  return enabled && pstjit::mode() != pstjit::Mode::Off && synthetic_stream_sig(size, n_attrs, dst_aos, dst_stride, dst_covered, &sig);
+  return filter_stream_enabled() && pstjit::mode() != pstjit::Mode::Off && synthetic_stream_sig(size, n_attrs, dst_aos, dst_stride, dst_covered, &sig);
 }
 std::string filter_stream_source(const uint32_t* size, int n_attrs, bool dst_aos, uint32_t dst_stride, bool dst_covered, const FilterPredicate* pred) {
   StreamSig sig;
@@ -804,7 +807,7 @@ void launch_filter_scan(uint64_t n, uint32_t tile, uint8_t* workspace, const uns
   const uint32_t n_tiles = (uint32_t)((n + tile - 1) / tile);
   unsigned long long* offsets = (unsigned long long*)workspace;
   uint32_t* counts = (uint32_t*)(workspace + ((size_t)n_tiles + 1) * sizeof(unsigned long long));
-  static const bool scan_blocks = [] { const char* v = std::getenv("PST_FILTER_SCAN_BLOCKS"); return !(v && *v == '0'); }();  // (0: the one-block scan, the A/B)
+  static const bool scan_blocks = pst::env_on("PST_FILTER_SCAN_BLOCKS");  // (0: the one-block scan, the A/B)
   if (scan_blocks && n_tiles > kScanBlockTiles && n_tiles <= (1u << 19))
     hipLaunchKernelGGL(tile_scan_blocks_kernel, dim3((n_tiles + kScanBlockTiles - 1) / kScanBlockTiles), dim3(kScanBlockTiles), 0, stream, (const uint32_t*)counts, n_tiles,
                        offsets, total_also);
@@ -879,11 +882,10 @@ bool launch_filter_scatter(const uint8_t* mask_dev, uint64_t n, uint32_t tile, u
     // 2. (PST_FILTER_STREAM=0 only: the A/B forms of rounds 2-3) the bench layout into records with compile-time attribute lists on the GATHER
     //    side: point-major record assembly (filter_big_records_kernel: same-box A/B against the granule-major constants 0.657 -> 0.673 of peak,
     //    0.680 with a 24 KiB record tile), PST_FILTER_PM=0 the granule-major constants; the columnar target LOST with constants and has none.
-    static const bool static_plans_env = [] { const char* v = std::getenv("PST_STATIC_PLANS"); return !(v && *v == '0'); }();
-    const bool static_plans = static_plans_env && pstjit::mode() != pstjit::Mode::Off;
+    const bool static_plans = static_plans_enabled() && pstjit::mode() != pstjit::Mode::Off;
     if (static_plans && dst_aos && n_attrs <= kMaxFilterAttrs && filter_plan_equals<BigFilterPlan>(a, dst_aos)) {
       note_plan_kind(PST_PLAN_STATIC);
-      static const int pm = [] { const char* v = std::getenv("PST_FILTER_PM"); return v && *v ? std::atoi(v) : 1; }();
+      static const int pm = (int)pst::env_long("PST_FILTER_PM", 1);
       if (pm) {
         FilterArgs b = a;
         b.chunk = filter_chunk(dst_stride, 24L * 1024L);

@@ -92,9 +92,10 @@ size_t filter_into(const pst_buffer& src, pst_buffer& dst, const uint8_t* mask, 
   size_t covered = 0;
   for (size_t a = 0; a < na; ++a) {
     const Member& m = src.layout.members[a];
-    src_addr[a] = src.columnar ? col_addr(src, a, 0) : aos_addr(src, 0) + m.offset;
-    src_stride[a] = (uint32_t)(src.columnar ? m.size : src.layout.size);
-    dst_addr[a] = out->columnar ? col_addr(*out, a, 0) : 0;
+    const AttrView sv = attr_view(src, a);
+    src_addr[a] = sv.addr;
+    src_stride[a] = (uint32_t)sv.stride;
+    dst_addr[a] = out->columnar ? col_addr(*out, a, 0) : 0;  // interleaved target: the records' base and dst_off instead
     dst_off[a] = (uint32_t)m.offset;
     size[a] = (uint32_t)m.size;
     covered += m.size;

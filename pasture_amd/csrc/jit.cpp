@@ -8,6 +8,7 @@
 // background thread (PST_JIT=async, the default): the first calls of a new plan are interpreted, later ones take the specialised
 // kernel; PST_JIT=sync compiles in the calling thread, PST_JIT=0 switches the whole thing off.  hipRTC is bound with dlopen at first
 // use, so the library loads (and interprets) where it is absent.
+#include "env.hpp"
 #include "jit.hpp"
 
 #include <dlfcn.h>
@@ -284,13 +285,13 @@ void compile_entry(const std::shared_ptr<Entry>& e) {
     e->state = Entry::Failed;
     e->error = err;
     c.st.failures++;
-    if (std::getenv("PST_JIT_DEBUG")) fprintf(stderr, "[pst jit] compilation failed:\n%s\n", err.c_str());
+    if (pst::env_str("PST_JIT_DEBUG")) fprintf(stderr, "[pst jit] compilation failed:\n%s\n", err.c_str());
   } else {
     e->code = std::move(code);
     e->state = Entry::Ready;
     if (from_disk) c.st.disk_hits++;
     else { c.st.compiled++; c.st.compile_seconds += secs; }
-    if (std::getenv("PST_JIT_DEBUG")) fprintf(stderr, "[pst jit] %s in %.2f s (%zu bytes)\n", from_disk ? "loaded from disk" : "compiled", secs, e->code.size());
+    if (pst::env_str("PST_JIT_DEBUG")) fprintf(stderr, "[pst jit] %s in %.2f s (%zu bytes)\n", from_disk ? "loaded from disk" : "compiled", secs, e->code.size());
   }
   c.cv.notify_all();
 }
@@ -327,10 +328,7 @@ Mode mode() {
   return m;
 }
 uint64_t min_points() {
-  static const uint64_t n = [] {
-    const char* v = std::getenv("PST_JIT_MIN_POINTS");
-    return v && *v ? (uint64_t)std::strtoull(v, nullptr, 10) : (uint64_t)1 << 20;
-  }();
+  static const uint64_t n = (uint64_t)pst::env_long("PST_JIT_MIN_POINTS", 1L << 20);
   return n;
 }
 
@@ -339,18 +337,13 @@ uint32_t QuadSpec::lds_bytes() const {
   return b < 256u ? 256u : b;
 }
 
-static long env_long(const char* name, long dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? std::strtol(v, nullptr, 10) : dflt;
-}
-
 bool spec_from_plan(const ConvertPlan& plan, bool src_aos, bool dst_aos, QuadSpec* spec) {
   const ConvertHeader& h = plan.h;
   if (!(src_aos || dst_aos) || h.in_place || h.n_entries == 0 || h.n_entries > PST_PLAN_MAX_ENTRIES) return false;
   if (src_aos && (h.src_aos & 15u)) return false;  // record tiles travel as 16-byte chunks
   if (dst_aos && (h.dst_aos & 15u)) return false;
   // the lane holds four records of either side in registers
-  static const long max_words = env_long("PST_JIT_MAX_WORDS", 224);
+  static const long max_words = pst::env_long("PST_JIT_MAX_WORDS", 224);
   QuadSpec s;
   s.src_aos = src_aos; s.dst_aos = dst_aos;
   s.src_stride = src_aos ? h.src_stride : 0; s.dst_stride = dst_aos ? h.dst_stride : 0;
@@ -360,12 +353,12 @@ bool spec_from_plan(const ConvertPlan& plan, bool src_aos, bool dst_aos, QuadSpe
   // LDS bytes per point.  Incoming regions: the source record tile, the staged wide source columns (and the target record tile when its
   // records are read-modify-written); outgoing regions: the target record tile, the staged wide target columns.  With `alias` the outgoing
   // regions overlay the incoming ones (one more barrier, half the LDS: twice the workgroups per CU).
-  static const long alias_env = env_long("PST_JIT_ALIAS", 0);
+  static const long alias_env = pst::env_long("PST_JIT_ALIAS", 0);
   s.alias = (alias_env != 0 && !(dst_aos && !s.covered)) ? 1u : 0u;
   uint32_t in_stage = s.src_stride, out_stage = 0;
   if (s.alias) { s.dst_tile_off = 0; out_stage = s.dst_stride; }
   else { s.dst_tile_off = s.src_stride; in_stage += s.dst_stride; }
-  static const long wide_min = env_long("PST_JIT_WIDE_MIN", 8);
+  static const long wide_min = pst::env_long("PST_JIT_WIDE_MIN", 8);
   auto wide = [&](uint32_t size, uint64_t col) { return (long)size >= wide_min && size % 4u == 0 && (col & 15u) == 0; };
   for (uint32_t m = 0; m < h.n_entries; ++m) {
     const PlanEntry& e = plan.e[m];
@@ -412,19 +405,19 @@ bool spec_from_plan(const ConvertPlan& plan, bool src_aos, bool dst_aos, QuadSpe
   // tile = 4 x lanes points.  ONE WAVE per workgroup (256 points) measured best on every pairing (10^8 points, eight random layouts x three
   // pairings: 64 lanes 0.74-0.80 of peak, 128 lanes 0.51-0.80, 256 lanes 0.26-0.77): the three phases of a tile -- request, shuffle, store --
   // need no barrier inside one wave, a CU holds 4-12 tiles in different phases instead of 1-3, and a tile of records is 6-25 KiB of LDS.
-  static const long blk_env = env_long("PST_JIT_BLK", 64);
+  static const long blk_env = pst::env_long("PST_JIT_BLK", 64);
   s.blk = (blk_env == 64 || blk_env == 128 || blk_env == 256 || blk_env == 512) ? (int)blk_env : 64;
   if (s.lds_bytes() > 160u * 1024u - 1024u) return false;
   if (h.n < s.tile()) return false;
   // XCD-aware tile numbering (every XCD works on one contiguous eighth of the range): with one small tile per workgroup it pays on all
   // three pairings (same run as above: means 0.726 / 0.726 -> 0.770 / 0.767 for columns -> records and records -> records, 0.763 -> 0.774 for
   // records -> columns)
-  static const long xcd_env = env_long("PST_JIT_XCD", 1);
+  static const long xcd_env = pst::env_long("PST_JIT_XCD", 1);
   s.xcd = xcd_env != 0 ? 1u : 0u;
   // non-temporal accesses: bit 0 narrow column loads, 1 narrow column stores, 2 tile stores (LDS -> HBM), 3 tile loads (LDS-DMA).  Same-box
   // sweep (12 random layouts x 3 pairings, 10^8 points, means): all four 0.810 / 0.785 / 0.806 (records -> columns / columns -> records /
   // records -> records); without the DMA bit 0.776 / 0.775 / 0.779; none 0.770 / 0.752 / 0.772: a tile is read once, by one wave.
-  static const long nt_env = env_long("PST_JIT_NT", -1);
+  static const long nt_env = pst::env_long("PST_JIT_NT", -1);
   s.nt = nt_env >= 0 ? (uint32_t)nt_env & 15u : 15u;
   *spec = std::move(s);
   return true;

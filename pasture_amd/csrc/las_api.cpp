@@ -28,8 +28,9 @@ void encode_range(const pst_buffer* src, size_t src_first, size_t count, uint32_
   uint32_t stride[24], esize[24];
   const size_t na = typed.members.size();
   for (size_t a = 0; a < na; ++a) {
-    base[a] = src->columnar ? col_addr(*src, a, src_first) : aos_addr(*src, src_first) + typed.members[a].offset;
-    stride[a] = (uint32_t)(src->columnar ? typed.members[a].size : typed.size);
+    const AttrView v = attr_view(*src, a, src_first);
+    base[a] = v.addr;
+    stride[a] = (uint32_t)v.stride;
     esize[a] = (uint32_t)typed.members[a].size;
   }
   uint8_t* scratch = workspace().partials(pstk::las_encode_workspace_bytes());

@@ -16,6 +16,7 @@
 // leaves with 16-byte coalesced stores.  The header reductions (6-double AABB with the header's current bounds as seeds,
 // 15 return counters, out-of-range count) are folded per wave -> per block -> one fold kernel.  HBM-bound; no MFMA.
 #include "device_common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 #include "las_device.hpp"
 #include "tile_io.hpp"
@@ -418,7 +419,7 @@ constexpr uint32_t kMaxGrid = 16384, kFoldGrid = 64;
 // the division sequence, 0.967 ms with the reciprocal, IQRs overlapping --: the encoder is bound by LDS / vector-memory issue (r04_sq_cycles.txt),
 // not by its vector arithmetic, so the form that needs no proof stays the default.
 static bool las_encode_fast_div_allowed() {
-  const char* e = std::getenv("PST_LAS_RECIPROCAL_DIV");
+  const char* e = pst::env_str("PST_LAS_RECIPROCAL_DIV");
   return e && e[0] == '1';
 }
 size_t las_encode_workspace_bytes() { return (size_t)(kMaxGrid + kFoldGrid) * (6 * sizeof(double) + kReturnSlots * sizeof(unsigned long long)); }

@@ -18,9 +18,7 @@ const Member& checked_position(const pst_buffer& b, size_t k) {
   if (b.len < 3)  // :86-88
     throw Error(PST_ERR_TOO_FEW_POINTS, "The point cloud is too small. Please use a point cloud that has 3 or more points!");
   if (k < 3) throw Error(PST_ERR_K_TOO_SMALL, "The k nearest neigbors attribute is too small!");  // :89-91
-  AttributeDef pos{"Position3D", DataType{}};
-  pos.datatype.kind = PST_VEC3F64;
-  const Member* m = b.layout.find(pos);  // view_attribute::<Vector3<f64>>(&POSITION_3D): exact (name, datatype) :97
+  const Member* m = position_vec3f64(b);  // view_attribute::<Vector3<f64>>(&POSITION_3D): exact (name, datatype) :97
   if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
   if (k > 64) throw Error(PST_ERR_UNSUPPORTED, "pst_compute_normals: k > 64 is not supported by the register-resident k-best list");
   if (b.len >= 0xFFFFFFF0ull)  // sorted indices and directory entries of the spatial index are uint32_t
@@ -37,6 +35,19 @@ void raise_degenerate(long long rc) {
                 "neighborhood is not enough to span a plane!\" (" + std::to_string(rc) + " neighbourhoods)");
 }
 
+struct NormalTargets { uint64_t base, stride, na, nst, ca, cst; };
+NormalTargets resolve_normal_targets(const pst_buffer& b, size_t k, pst_buffer& dst) {
+  const Member& pm = checked_position(b, k);
+  if (dst.len != b.len) throw Error(PST_ERR_RANGE, "target buffer length must equal the point cloud length");
+  AttributeDef nd{"Normal", DataType{}}, cd{"Curvature", DataType{}};
+  nd.datatype.kind = PST_VEC3F32;
+  cd.datatype.kind = PST_F64;
+  const Member *nm = dst.layout.find(nd), *cm = dst.layout.find(cd);
+  if (!nm && !cm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "target PointLayout has neither Normal (Vec3f32) nor Curvature (F64)");
+  const AttrView p = attr_view(b, &pm), nv = attr_view(dst, nm), cv = attr_view(dst, cm);
+  return NormalTargets{p.addr, p.stride, nv.addr, nv.stride, cv.addr, cv.stride};
+}
+
 }  // namespace
 
 extern "C" {
@@ -48,9 +59,7 @@ int pst_compute_normals(const pst_buffer* b, size_t k, double* out_normals, doub
   ensure_device();
   hipStream_t s = current_stream();
   const size_t n = b->len;
-  const size_t slot = (size_t)(&pm - b->layout.members.data());
-  const uint64_t base = b->columnar ? col_addr(*b, slot, 0) : aos_addr(*b, 0) + pm.offset;
-  const uint64_t stride = b->columnar ? pm.size : b->layout.size;
+  const auto [base, stride] = attr_view(*b, &pm);
   TempDev d_normals(n * 24), d_curv(n * 8), d_knn(out_knn ? n * k * 8 : 0);
   raise_degenerate(pstk::run_normals((const uint8_t*)(uintptr_t)base, stride, n, (uint32_t)k, (double*)d_normals.p, (double*)d_curv.p,
                                      (long long*)d_knn.p, nullptr, 0, 0, 0, 0, s));
@@ -67,28 +76,10 @@ int pst_compute_normals_into(const pst_buffer* b, size_t k, pst_buffer* dst) {
   PST_API_BEGIN
   not_null(b, "buffer");
   not_null(dst, "dst");
-  const Member& pm = checked_position(*b, k);
-  if (dst->len != b->len) throw Error(PST_ERR_RANGE, "target buffer length must equal the point cloud length");
-  AttributeDef nd{"Normal", DataType{}}, cd{"Curvature", DataType{}};
-  nd.datatype.kind = PST_VEC3F32;
-  cd.datatype.kind = PST_F64;
-  const int ns = dst->layout.index_of(nd), cs = dst->layout.index_of(cd);
-  if (ns < 0 && cs < 0) throw Error(PST_ERR_MISSING_ATTRIBUTE, "target PointLayout has neither Normal (Vec3f32) nor Curvature (F64)");
+  const NormalTargets t = resolve_normal_targets(*b, k, *dst);
   ensure_device();
   hipStream_t s = current_stream();
-  const size_t slot = (size_t)(&pm - b->layout.members.data());
-  const uint64_t base = b->columnar ? col_addr(*b, slot, 0) : aos_addr(*b, 0) + pm.offset;
-  const uint64_t stride = b->columnar ? pm.size : b->layout.size;
-  auto attr_addr = [&](int sl, uint64_t& addr, uint64_t& st) {
-    if (sl < 0) { addr = 0; st = 0; return; }
-    const Member& m = dst->layout.members[(size_t)sl];
-    addr = dst->columnar ? col_addr(*dst, (size_t)sl, 0) : aos_addr(*dst, 0) + m.offset;
-    st = dst->columnar ? m.size : dst->layout.size;
-  };
-  uint64_t na, nst, ca, cst;
-  attr_addr(ns, na, nst);
-  attr_addr(cs, ca, cst);
-  raise_degenerate(pstk::run_normals((const uint8_t*)(uintptr_t)base, stride, b->len, (uint32_t)k, nullptr, nullptr, nullptr, nullptr, na, nst, ca, cst, s));
+  raise_degenerate(pstk::run_normals((const uint8_t*)(uintptr_t)t.base, t.stride, b->len, (uint32_t)k, nullptr, nullptr, nullptr, nullptr, t.na, t.nst, t.ca, t.cst, s));
   PST_API_END
 }
 
@@ -101,9 +92,7 @@ int pst_compute_normals_device(const pst_buffer* b, size_t k, double* d_normals,
   if (!d_normals && !d_curvature && !d_knn) throw Error(PST_ERR_INVALID_ARGUMENT, "pst_compute_normals_device: no output requested");
   ensure_device();
   hipStream_t s = current_stream();
-  const size_t slot = (size_t)(&pm - b->layout.members.data());
-  const uint64_t base = b->columnar ? col_addr(*b, slot, 0) : aos_addr(*b, 0) + pm.offset;
-  const uint64_t stride = b->columnar ? pm.size : b->layout.size;
+  const auto [base, stride] = attr_view(*b, &pm);
   raise_degenerate(pstk::run_normals((const uint8_t*)(uintptr_t)base, stride, b->len, (uint32_t)k, d_normals, d_curvature, nullptr, d_knn, 0, 0, 0, 0, s));
   PST_API_END
 }
@@ -115,32 +104,6 @@ struct pst_normals_plan {
   int device = 0;  // the plan's scratch lives there
   ~pst_normals_plan() { if (plan) pstk::knn_plan_free(plan); }
 };
-
-namespace {
-struct NormalTargets { uint64_t base, stride, na, nst, ca, cst; };
-NormalTargets resolve_normal_targets(const pst_buffer& b, size_t k, pst_buffer& dst) {
-  const Member& pm = checked_position(b, k);
-  if (dst.len != b.len) throw Error(PST_ERR_RANGE, "target buffer length must equal the point cloud length");
-  AttributeDef nd{"Normal", DataType{}}, cd{"Curvature", DataType{}};
-  nd.datatype.kind = PST_VEC3F32;
-  cd.datatype.kind = PST_F64;
-  const int ns = dst.layout.index_of(nd), cs = dst.layout.index_of(cd);
-  if (ns < 0 && cs < 0) throw Error(PST_ERR_MISSING_ATTRIBUTE, "target PointLayout has neither Normal (Vec3f32) nor Curvature (F64)");
-  const size_t slot = (size_t)(&pm - b.layout.members.data());
-  NormalTargets t{};
-  t.base = b.columnar ? col_addr(b, slot, 0) : aos_addr(b, 0) + pm.offset;
-  t.stride = b.columnar ? pm.size : b.layout.size;
-  auto attr_addr = [&](int sl, uint64_t& addr, uint64_t& st) {
-    if (sl < 0) { addr = 0; st = 0; return; }
-    const Member& m = dst.layout.members[(size_t)sl];
-    addr = dst.columnar ? col_addr(dst, (size_t)sl, 0) : aos_addr(dst, 0) + m.offset;
-    st = dst.columnar ? m.size : dst.layout.size;
-  };
-  attr_addr(ns, t.na, t.nst);
-  attr_addr(cs, t.ca, t.cst);
-  return t;
-}
-}  // namespace
 
 // One synchronous pst_compute_normals_into (dst holds its results) whose decisions -- frame, grid, box shape, capacities -- are kept.
 int pst_compute_normals_plan_create(const pst_buffer* b, size_t k, pst_buffer* dst, pst_normals_plan** out) {

@@ -38,24 +38,17 @@ void sample_indices(uint64_t seed, uint64_t n, size_t iterations, uint32_t per, 
   }
 }
 
-struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };
+struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };  // an AttrView as the kernels take it, and the number of points
 
-// view_attribute::<Vector3<f64>>(&POSITION_3D): name AND datatype (buffer_views.rs:301-310)
 const Member* position_member(const pst_buffer& b) {
-  DataType v3;
-  v3.kind = PST_VEC3F64;
-  const int slot = b.layout.index_of(AttributeDef{"Position3D", v3});
-  if (slot < 0) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute Position3D (Vec3f64) not found in PointLayout of buffer");
-  return &b.layout.members[(size_t)slot];
+  const Member* m = position_vec3f64(b);
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute Position3D (Vec3f64) not found in PointLayout of buffer");
+  return m;
 }
 PosView position_view(const pst_buffer& b, const Member* m) {
-  const size_t slot = (size_t)(m - b.layout.members.data());
   if (b.len >= 0xFFFFFFFFull) throw Error(PST_ERR_UNSUPPORTED, "ransac: 2^32 - 1 points and more per call are not supported");
-  PosView v;
-  v.base = b.len == 0 ? nullptr : (const uint8_t*)(uintptr_t)(b.columnar ? col_addr(b, slot, 0) : aos_addr(b, 0) + m->offset);
-  v.stride = b.columnar ? m->size : b.layout.size;
-  v.n = b.len;
-  return v;
+  const AttrView v = attr_view(b, m);
+  return PosView{b.len == 0 ? nullptr : (const uint8_t*)(uintptr_t)v.addr, v.stride, b.len};
 }
 
 struct Scratch {

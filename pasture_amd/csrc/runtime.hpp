@@ -53,7 +53,7 @@ Workspace& workspace();
 // into the pinned mirror -- host memory the device addresses -- instead of into device memory and copied out by one more launch (a blit kernel per
 // hipMemcpyAsync).  PST_RESULTS_TO_HOST=0: the copy (the A/B switch).
 inline bool results_to_host() {
-  static const bool on = [] { const char* v = std::getenv("PST_RESULTS_TO_HOST"); return !(v && *v == '0'); }();
+  static const bool on = env_on("PST_RESULTS_TO_HOST");
   return on;
 }
 
@@ -83,6 +83,23 @@ void bump_epoch(pst_buffer& b);  // the storage of an owning buffer is about to 
 inline uint64_t aos_addr(const pst_buffer& b, size_t point) { return (uint64_t)(uintptr_t)b.data + (uint64_t)point * b.layout.size; }
 inline uint64_t col_addr(const pst_buffer& b, size_t slot, size_t point) {
   return (uint64_t)(uintptr_t)b.columns[slot] + (uint64_t)point * b.layout.members[slot].size;
+}
+// where the values of one attribute are: the address of point `first`'s value and the distance in bytes to the next point's
+struct AttrView { uint64_t addr; uint64_t stride; };
+inline AttrView attr_view(const pst_buffer& b, size_t slot, size_t first = 0) {
+  const Member& m = b.layout.members[slot];
+  return b.columnar ? AttrView{col_addr(b, slot, first), m.size} : AttrView{aos_addr(b, first) + m.offset, b.layout.size};
+}
+// m: a member of b's own layout, or null for an attribute the layout does not have => {0, 0}
+inline AttrView attr_view(const pst_buffer& b, const Member* m, size_t first = 0) {
+  return m ? attr_view(b, (size_t)(m - b.layout.members.data()), first) : AttrView{0, 0};
+}
+// view_attribute::<Vector3<f64>>(&POSITION_3D): exact name AND datatype (buffer_views.rs:301-310); null when the layout has none (each caller
+// throws the message of the panic it mirrors)
+inline const Member* position_vec3f64(const pst_buffer& b) {
+  AttributeDef pos{"Position3D", DataType{}};
+  pos.datatype.kind = PST_VEC3F64;
+  return b.layout.find(pos);
 }
 
 // Plan execution: `entries` hold per-mapping descriptors with src_col/dst_col already resolved; the function splits them

@@ -21,6 +21,7 @@
 // Since round 5 the kernel in THIS file serves the read-only modes (AABB, AABB of the transformed values) as a persistent grid; every mode that
 // writes runs the one-tile-per-block body of stream_tile.hpp (rotated accumulators, LDS block fold, few bytes in flight per CU).
 #include "device_common.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 #include "stream_tile.hpp"
 #include "zero_sign.hpp"
@@ -359,20 +360,20 @@ int reduce_grid() { return device_cus() * 8; }
 size_t minmax_partials_bytes() { return (size_t)(reduce_grid() + kFoldBlocks) * 6 * sizeof(double); }
 
 static bool stream_xcd_aware() {
-  static const bool on = [] { const char* v = std::getenv("PST_STREAM_XCD"); return !(v && *v == '0'); }();  // on by default: each XCD streams one contiguous eighth
+  static const bool on = pst::env_on("PST_STREAM_XCD");  // on by default: each XCD streams one contiguous eighth
   return on;
 }
 // shape of the writing modes: loads per lane, threads per block, blocks resident per CU
 struct StreamShape { int loads, block, resident; };
 static StreamShape stream_shape(unsigned mode) {
   StreamShape s = (mode & 4u) ? StreamShape{3, 512, 2} : StreamShape{3, 256, 2};
-  static const int cap = [] { const char* v = std::getenv("PST_STREAM_RESIDENT"); return v && *v ? std::atoi(v) : 0; }();  // same-box A/Bs
+  static const int cap = (int)pst::env_long("PST_STREAM_RESIDENT", 0);  // same-box A/Bs
   if (cap > 0) s.resident = cap;
   return s;
 }
 unsigned lds_per_cu();
 uint32_t lds_with_resident_cap(size_t lds_bytes, int resident) {
-  static const int forced = [] { const char* v = std::getenv("PST_RESIDENT"); return v && *v ? std::atoi(v) : -1; }();
+  static const int forced = (int)pst::env_long("PST_RESIDENT", -1);
   if (forced >= 0) resident = forced;
   if (resident <= 0 || resident >= 32) return (uint32_t)lds_bytes;
   const size_t want = lds_per_cu() / (unsigned)(resident + 1) + 64u;

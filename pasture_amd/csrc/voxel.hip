@@ -23,6 +23,7 @@
 
 #include "device_common.hpp"
 #include "device_sort.hpp"
+#include "env.hpp"
 #include "kernels.hpp"
 
 using namespace pstd;
@@ -752,7 +753,7 @@ bool voxel_grid_reduce(VoxelGridState* st, const uint64_t* src_addr, const uint3
   const uint64_t groups = (st->n_voxels + 63) / 64;
   if (groups == 0) return hipGetLastError() == hipSuccess;
   if (groups > 0x7FFFFFFFull) return false;
-  static const uint32_t cap_env = [] { const char* e = std::getenv("PST_VOXEL_STAGE"); return e && *e ? (uint32_t)std::strtoul(e, nullptr, 10) : ~0u; }();  // 0 = never stage (A/B)
+  static const uint32_t cap_env = (uint32_t)pst::env_long("PST_VOXEL_STAGE", -1);  // 0 = never stage (A/B)
   uint32_t cap = (uint32_t)std::min<uint64_t>(6144, std::max<uint64_t>(1024, (st->n * 8 / 5) / groups + 63)) & ~63u;
   if (cap_env != ~0u) cap = std::min<uint32_t>(cap_env, 6144) & ~63u;
   if (st->planned) cap = st->shape.stage_cap;  // (sized for the voxel count the plan measured, not for its capacity)

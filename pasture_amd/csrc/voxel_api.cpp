@@ -39,15 +39,13 @@ std::vector<double> create_markers(double mn, double mx, double leafsize) {
   return m;
 }
 
-const Member* find_member(const Layout& l, const char* name, uint32_t kind) {
-  for (auto& m : l.members)
-    if (m.def.name == name && m.def.datatype.kind == kind) return &m;
-  return nullptr;
-}
-const Member* find_by_name(const Layout& l, const char* name) {
-  for (auto& m : l.members)
-    if (m.def.name == name) return &m;
-  return nullptr;
+// :116-122
+AttrView checked_position(const pst_buffer& buffer) {
+  const Member* pos = position_vec3f64(buffer);
+  if (!pos)
+    throw Error(PST_ERR_MISSING_ATTRIBUTE,
+                "The PointBuffer does not have the attribute attributes::POSITION_3D which is needed for the creation of the voxel grid.");
+  return attr_view(buffer, pos);
 }
 
 // plan of set_all_attributes over the TARGET layout (:459-689); checked before any point is produced... the reference would panic at the
@@ -58,7 +56,7 @@ struct AttrPlan {
 };
 AttrPlan attribute_plan(const pst_buffer& buffer, const Layout& tl) {
   for (const char* w : kWaveform)
-    if (find_by_name(tl, w)) throw Error(PST_ERR_UNSUPPORTED_ATTRIBUTE, "Waveform data currently not supported!");
+    if (tl.find_by_name(w)) throw Error(PST_ERR_UNSUPPORTED_ATTRIBUTE, "Waveform data currently not supported!");
   const size_t na = tl.members.size();
   AttrPlan p;
   p.src_m.resize(na); p.reduce.resize(na); p.kind.resize(na);
@@ -68,7 +66,7 @@ AttrPlan attribute_plan(const pst_buffer& buffer, const Layout& tl) {
     for (auto& r : kRules)
       if (t.def.name == r.name && t.def.datatype.kind == r.kind) rule = &r;
     if (!rule) throw Error(PST_ERR_UNSUPPORTED_ATTRIBUTE, "attribute is non-standard which is not supported currently: " + t.def.name);
-    p.src_m[a] = find_member(buffer.layout, rule->name, rule->kind);  // view_attribute::<T>(&attributes::X) on the source
+    p.src_m[a] = buffer.layout.find(t.def);  // (the rule's name and datatype are the target's) view_attribute::<T>(&attributes::X) on the source
     if (!p.src_m[a]) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute " + t.def.name + " not found in PointLayout of buffer");
     p.reduce[a] = rule->reduce;
     p.kind[a] = rule->kind;
@@ -82,11 +80,9 @@ void run_reductions(pstk::VoxelGridState* st, const pst_buffer& buffer, pst_buff
   std::vector<uint64_t> src_addr(na), dst_addr(na);
   std::vector<uint32_t> src_stride(na), dst_stride(na);
   for (size_t a = 0; a < na; ++a) {
-    const size_t sslot = (size_t)(p.src_m[a] - buffer.layout.members.data());
-    src_addr[a] = buffer.columnar ? col_addr(buffer, sslot, 0) : aos_addr(buffer, 0) + p.src_m[a]->offset;
-    src_stride[a] = (uint32_t)(buffer.columnar ? p.src_m[a]->size : buffer.layout.size);
-    dst_addr[a] = filtered.columnar ? col_addr(filtered, a, 0) : aos_addr(filtered, 0) + tl.members[a].offset;
-    dst_stride[a] = (uint32_t)(filtered.columnar ? tl.members[a].size : tl.size);
+    const AttrView src = attr_view(buffer, p.src_m[a]), dst = attr_view(filtered, a);
+    src_addr[a] = src.addr; src_stride[a] = (uint32_t)src.stride;
+    dst_addr[a] = dst.addr; dst_stride[a] = (uint32_t)dst.stride;
   }
   if (na && !pstk::voxel_grid_reduce(st, src_addr.data(), src_stride.data(), dst_addr.data(), dst_stride.data(), p.reduce.data(), p.kind.data(), (int)na, first, s))
     throw hip_failure("voxel grid reduction failed: ");
@@ -97,42 +93,50 @@ struct StateGuard {
   ~StateGuard() { if (st) pstk::voxel_grid_free(st); }
 };
 
+// What pst_voxelgrid_filter and pst_voxelgrid_plan_create share: the checks, the cloud's bounds (:125), the markers of its axes and the grid built
+// over them.  target: the layout the reductions will fill (its attribute plan is checked between the markers and the build), or null.
+struct BuiltGrid {
+  double mn[3], mx[3];
+  std::vector<double> mk[3];  // markers of x, y, z
+  AttrView pos;
+  AttrPlan ap;
+  StateGuard g;
+  long long nv = 0;  // occupied voxels
+  hipStream_t s = nullptr;  // the current stream: everything above is enqueued there
+};
+void build_grid(BuiltGrid& r, const pst_buffer& buffer, const double leafs[3], const Layout* target) {
+  r.pos = checked_position(buffer);
+  const size_t n = buffer.len;
+  if (n == 0) throw Error(PST_ERR_BOUNDS_INVALID, "called `Option::unwrap()` on a `None` value");  // :125 calculate_bounds(buffer).unwrap()
+  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, "voxelgrid_filter: more than 2^32 - 17 points per call (sorted point indices are uint32_t)");
+  ensure_device();
+  hipStream_t s = r.s = current_stream();
+  Workspace& ws = workspace();
+  double* dev6 = (double*)(ws.dev + 2048);
+  bounds_of_range(buffer, 0, n, dev6, s);
+  PST_HIP_CHECK(hipMemcpyAsync(ws.pinned + 1024, dev6, 6 * sizeof(double), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  double rec[6];
+  std::memcpy(rec, ws.pinned + 1024, sizeof(rec));
+  check_bounds_record(rec, r.mn, r.mx);  // AABB::from_min_max inside calculate_bounds
+  for (int a = 0; a < 3; ++a) r.mk[a] = create_markers(r.mn[a], r.mx[a], leafs[a]);
+  if (target) r.ap = attribute_plan(buffer, *target);
+  r.nv = pstk::voxel_grid_build(r.g.st, (const uint8_t*)(uintptr_t)r.pos.addr, r.pos.stride, n, r.mk[0].data(), (uint32_t)r.mk[0].size(), r.mk[1].data(),
+                                (uint32_t)r.mk[1].size(), r.mk[2].data(), (uint32_t)r.mk[2].size(), r.mn, leafs, s);
+  if (r.nv < 0) throw hip_failure("voxel grid build failed: ");
+}
+
 }  // namespace
 
 extern "C" int pst_voxelgrid_filter(const pst_buffer* buffer, double leafsize_x, double leafsize_y, double leafsize_z, pst_buffer* filtered) {
   PST_API_BEGIN
   not_null(buffer, "buffer");
   not_null(filtered, "filtered");
-  const Member* pos = find_member(buffer->layout, "Position3D", PST_VEC3F64);
-  if (!pos)  // :116-122
-    throw Error(PST_ERR_MISSING_ATTRIBUTE,
-                "The PointBuffer does not have the attribute attributes::POSITION_3D which is needed for the creation of the voxel grid.");
-  const size_t n = buffer->len;
-  if (n == 0) throw Error(PST_ERR_BOUNDS_INVALID, "called `Option::unwrap()` on a `None` value");  // :125 calculate_bounds(buffer).unwrap()
-  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, "voxelgrid_filter: more than 2^32 - 17 points per call (sorted point indices are uint32_t)");
-  ensure_device();
-  hipStream_t s = current_stream();
-  Workspace& ws = workspace();
-  double* dev6 = (double*)(ws.dev + 2048);
-  bounds_of_range(*buffer, 0, n, dev6, s);
-  PST_HIP_CHECK(hipMemcpyAsync(ws.pinned + 1024, dev6, 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  double rec[6], mn[3], mx[3];
-  std::memcpy(rec, ws.pinned + 1024, sizeof(rec));
-  check_bounds_record(rec, mn, mx);  // AABB::from_min_max inside calculate_bounds
-  const std::vector<double> mkx = create_markers(mn[0], mx[0], leafsize_x), mky = create_markers(mn[1], mx[1], leafsize_y),
-                            mkz = create_markers(mn[2], mx[2], leafsize_z);
-
-  const AttrPlan ap = attribute_plan(*buffer, filtered->layout);
-
-  StateGuard g;
-  const size_t pslot = (size_t)(pos - buffer->layout.members.data());
-  const uint8_t* pos_base = buffer->columnar ? buffer->columns[pslot] : buffer->data + pos->offset;
-  const uint64_t pos_stride = buffer->columnar ? pos->size : buffer->layout.size;
   const double leafs[3] = {leafsize_x, leafsize_y, leafsize_z};
-  const long long nv = pstk::voxel_grid_build(g.st, pos_base, pos_stride, n, mkx.data(), (uint32_t)mkx.size(), mky.data(), (uint32_t)mky.size(), mkz.data(),
-                                              (uint32_t)mkz.size(), mn, leafs, s);
-  if (nv < 0) throw hip_failure("voxel grid build failed: ");
+  BuiltGrid grid;
+  build_grid(grid, *buffer, leafs, &filtered->layout);
+  const long long nv = grid.nv;
+  hipStream_t s = grid.s;
 
   // filtered_buffer.push_points(centroid) per voxel :161-164 == append nv zero-initialised points and fill the attributes
   const size_t old_len = filtered->len;
@@ -141,7 +145,7 @@ extern "C" int pst_voxelgrid_filter(const pst_buffer* buffer, double leafsize_x,
     filtered->len = old_len;
   }
   resize_buffer(*filtered, old_len + (size_t)nv, true);  // UntypedPointBuffer::new zero-fills; padding stays zero
-  run_reductions(g.st, *buffer, *filtered, ap, old_len, s);
+  run_reductions(grid.g.st, *buffer, *filtered, grid.ap, old_len, s);
   // no final synchronisation: nothing is returned to host memory (include/pasture_amd.h conventions); the reductions and the
   // stream-ordered release of the grid state stay in flight on the current stream -- a third host round trip per call would triple
   // the cost of a loaded host (8 ms -> 40+ ms measured with three)
@@ -166,40 +170,19 @@ extern "C" int pst_voxelgrid_plan_create(const pst_buffer* buffer, double leafsi
   PST_API_BEGIN
   not_null(buffer, "buffer");
   not_null(out, "out");
-  const Member* pos = find_member(buffer->layout, "Position3D", PST_VEC3F64);
-  if (!pos)
-    throw Error(PST_ERR_MISSING_ATTRIBUTE,
-                "The PointBuffer does not have the attribute attributes::POSITION_3D which is needed for the creation of the voxel grid.");
-  const size_t n = buffer->len;
-  if (n == 0) throw Error(PST_ERR_BOUNDS_INVALID, "called `Option::unwrap()` on a `None` value");
-  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, "voxelgrid_filter: more than 2^32 - 17 points per call (sorted point indices are uint32_t)");
-  ensure_device();
-  hipStream_t s = current_stream();
-  Workspace& ws = workspace();
   // ONE synchronous pass over this cloud: its bounds, the marker counts of its axes and its number of occupied voxels size the plan
-  double* dev6 = (double*)(ws.dev + 2048);
-  bounds_of_range(*buffer, 0, n, dev6, s);
-  PST_HIP_CHECK(hipMemcpyAsync(ws.pinned + 1024, dev6, 6 * sizeof(double), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  double rec[6], mn[3], mx[3];
-  std::memcpy(rec, ws.pinned + 1024, sizeof(rec));
-  check_bounds_record(rec, mn, mx);
-  const std::vector<double> mkx = create_markers(mn[0], mx[0], leafsize_x), mky = create_markers(mn[1], mx[1], leafsize_y),
-                            mkz = create_markers(mn[2], mx[2], leafsize_z);
-  StateGuard g;
-  const size_t pslot = (size_t)(pos - buffer->layout.members.data());
-  const uint8_t* pos_base = buffer->columnar ? buffer->columns[pslot] : buffer->data + pos->offset;
-  const uint64_t pos_stride = buffer->columnar ? pos->size : buffer->layout.size;
   const double leafs[3] = {leafsize_x, leafsize_y, leafsize_z};
-  const long long nv = pstk::voxel_grid_build(g.st, pos_base, pos_stride, n, mkx.data(), (uint32_t)mkx.size(), mky.data(), (uint32_t)mky.size(), mkz.data(),
-                                              (uint32_t)mkz.size(), mn, leafs, s);
-  if (nv < 0) throw hip_failure("voxel grid build failed: ");
+  BuiltGrid grid;
+  build_grid(grid, *buffer, leafs, nullptr);
+  const size_t n = buffer->len;
+  const long long nv = grid.nv;
+  hipStream_t s = grid.s;
   stream_sync(s);
   // capacities: an eighth more markers per axis (a later cloud of the same shape may be a little larger), a quarter more voxels
   auto plan = std::make_unique<pst_voxel_plan>();
   pstk::VoxelPlanShape& sh = plan->shape;
   sh.n = n;
-  const size_t counts[3] = {mkx.size(), mky.size(), mkz.size()};
+  const size_t counts[3] = {grid.mk[0].size(), grid.mk[1].size(), grid.mk[2].size()};
   size_t total = 0;
   for (int a = 0; a < 3; ++a) {
     const size_t cap = counts[a] + std::max<size_t>(8, counts[a] / 8);
@@ -234,10 +217,7 @@ extern "C" int pst_voxelgrid_filter_async(pst_voxel_plan* plan, const pst_buffer
   not_null(buffer, "buffer");
   not_null(filtered, "filtered");
   not_null(device_count_and_status, "device_count_and_status");
-  const Member* pos = find_member(buffer->layout, "Position3D", PST_VEC3F64);
-  if (!pos)
-    throw Error(PST_ERR_MISSING_ATTRIBUTE,
-                "The PointBuffer does not have the attribute attributes::POSITION_3D which is needed for the creation of the voxel grid.");
+  const AttrView pos = checked_position(*buffer);
   if (buffer->len != plan->shape.n)
     throw Error(PST_ERR_INVALID_ARGUMENT, "voxelgrid_filter_async: the plan was made for " + std::to_string(plan->shape.n) + " points, the buffer holds " +
                                               std::to_string(buffer->len));
@@ -252,10 +232,7 @@ extern "C" int pst_voxelgrid_filter_async(pst_voxel_plan* plan, const pst_buffer
     throw Error(PST_ERR_INVALID_ARGUMENT, "voxelgrid_filter_async: the plan was made on device " + std::to_string(plan->device) + ", the current device is " + std::to_string(dev));
   hipStream_t s = current_stream();
   bounds_of_range(*buffer, 0, buffer->len, plan->bounds6, s, plan->partials);
-  const size_t pslot = (size_t)(pos - buffer->layout.members.data());
-  const uint8_t* pos_base = buffer->columnar ? buffer->columns[pslot] : buffer->data + pos->offset;
-  const uint64_t pos_stride = buffer->columnar ? pos->size : buffer->layout.size;
-  if (!pstk::voxel_grid_build_async(plan->st, pos_base, pos_stride, plan->bounds6, (unsigned long long*)device_count_and_status, s))
+  if (!pstk::voxel_grid_build_async(plan->st, (const uint8_t*)(uintptr_t)pos.addr, pos.stride, plan->bounds6, (unsigned long long*)device_count_and_status, s))
     throw hip_failure("voxel grid build failed: ");
   run_reductions(plan->st, *buffer, *filtered, ap, dst_first, s);
   PST_API_END
