@@ -9,6 +9,10 @@ namespace pstk {
 
 // stable LSD radix sort of (key, value) pairs on key bits [0, end_bit); n < 2^32.  BOTH pairs of buffers are scratch (the passes
 // alternate between them); the result is in (keys_out, vals_out).  radix_sort.hip: one, three or four passes for 32-bit keys.
+// Bits at and above end_bit are IGNORED AND PRESERVED: they take no part in the order (keys that agree below end_bit stay in input order whatever
+// their higher bits) and every key arrives whole.  end_bit 0 orders by nothing: the pairs are copied in input order.  n == 0 writes nothing; a
+// `bytes` below what the size query returned is hipErrorInvalidValue before anything is launched.  Nothing outside [0, n) of the four arrays and
+// `bytes` of the scratch is written; the scratch need not be cleared between calls.  (tests/test_device_sort.py pins all of this.)
 // iota: the values are the element numbers 0 .. n-1 -- vals_in is not read (it stays scratch).  first: what sort_first_pass returned for the
 // same (tmp, n, end_bit) when the caller's key kernel has left the first pass's histogram there, else nullptr.
 struct RadixFirstPass { uint32_t* counts; uint32_t tiles, bits, tile_size; };  // counts == nullptr: not offered (the library sort is in use)

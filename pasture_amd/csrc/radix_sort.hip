@@ -158,6 +158,7 @@ __global__ __launch_bounds__(kThreads, 4) void radix_scatter_kernel(const KeyT* 
   // ---- rank within the wave, item by item (memory order) -----------------------------------------------------------------------------
   uint16_t rank[kItems];
   const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64u - lane));  // lanes below this one
+  [[maybe_unused]] uint32_t seen_all = 0;
 #pragma unroll
   for (int i = 0; i < kItems; ++i) {
     const bool valid = e0 + (uint32_t)i * 64u < tile_n;
@@ -169,10 +170,17 @@ __global__ __launch_bounds__(kThreads, 4) void radix_scatter_kernel(const KeyT* 
       peers &= ((d >> b) & 1u) ? m : ~m;
     }
     const uint32_t below = (uint32_t)__builtin_popcountll(peers & lt);
-    const uint32_t seen = wcount[wave][d];  // (every peer reads the counter before its lowest lane advances it: one wave, program order)
-    if (valid && below == 0) wcount[wave][d] = (uint16_t)(seen + (uint32_t)__builtin_popcountll(peers));
+    uint32_t seen;
+    if constexpr (BITS == 0) {  // one digit (end_bit 0): the count so far is the same in every lane and stays in a register -- a counter at ONE fixed
+      seen = seen_all;          // LDS address that one lane writes and all read is, to the compiler, a lane's own store followed by its own load
+      seen_all += (uint32_t)__builtin_popcountll(peers);
+    } else {
+      seen = wcount[wave][d];  // (every peer reads the counter before its lowest lane advances it: one wave, program order)
+      if (valid && below == 0) wcount[wave][d] = (uint16_t)(seen + (uint32_t)__builtin_popcountll(peers));
+    }
     rank[i] = (uint16_t)(seen + below);
   }
+  if constexpr (BITS == 0) { if (lane == 0) wcount[wave][0] = (uint16_t)seen_all; }
   __syncthreads();
   // ---- per digit: keys of earlier waves, the tile's count; then the digit's first position in the tile and in the output ----------
   uint32_t mine = 0;  // the tile's number of keys with digit `tid` (RADIX <= kThreads: one digit per thread)
@@ -229,7 +237,8 @@ Plan plan_for(size_t n, unsigned end_bit, int tile = kTile) {
   // <= 8 bits and one copy of the result into the second pair (two 4 n-byte copies: 0.15 ms per 10^8 pairs, less than a fifth pass);
   // beyond 32 bits (64-bit keys) as many passes of <= 9 bits as the key needs
   p.passes = end_bit <= 9 ? 1u : (end_bit <= 27 ? 3u : (end_bit <= 32 ? 4u : (end_bit + 8u) / 9u));
-  unsigned left = end_bit ? end_bit : 1u;
+  // (end_bit 0: one pass of a ZERO-bit digit -- every key is digit 0, the pass copies the pairs in input order: no key bit takes part)
+  unsigned left = end_bit;
   for (unsigned i = 0; i < p.passes; ++i) { p.bits[i] = (left + (p.passes - i) - 1) / (p.passes - i); left -= p.bits[i]; }
   p.tiles = (uint32_t)((n + (size_t)tile - 1) / (size_t)tile);
   p.counts_bytes = ((size_t)kMaxRadix * (p.tiles ? p.tiles : 1u) * 4 + 255) & ~(size_t)255;
@@ -277,7 +286,7 @@ static hipError_t radix_sort_pairs_any(void* tmp, size_t& bytes, KeyT* keys_a, K
     else hipLaunchKernelGGL((radix_scatter_kernel<KeyT, B, false>), dim3(grid), dim3(kThreads), 0, stream, (const KeyT*)ki, (const uint32_t*)vi, (uint64_t)n, shift, p.tiles, counts, dbase, ko, vo);               \
     break;
     switch (b) {
-      PST_SCATTER(1) PST_SCATTER(2) PST_SCATTER(3) PST_SCATTER(4) PST_SCATTER(5) PST_SCATTER(6) PST_SCATTER(7) PST_SCATTER(8) PST_SCATTER(9)
+      PST_SCATTER(0) PST_SCATTER(1) PST_SCATTER(2) PST_SCATTER(3) PST_SCATTER(4) PST_SCATTER(5) PST_SCATTER(6) PST_SCATTER(7) PST_SCATTER(8) PST_SCATTER(9)
       default: return hipErrorInvalidValue;
     }
 #undef PST_SCATTER
