@@ -1,6 +1,6 @@
 // Test-only C forwarders to the sorts and scans of pasture_amd/csrc/device_sort.hpp (tests/sort_hooks.py loads them with ctypes;
 // tests/test_device_sort.py is the user).  No kernels, no logic: every function hands its arguments on.  Built by pasture_amd/csrc/Makefile
-// into tests/cpp/libpst_sort_hooks.so, linked against libpasture_amd.so; none of these names is part of the product's C ABI.
+// into pasture_amd/csrc/build/libpst_sort_hooks.so, linked against libpasture_amd.so; none of these names is part of the product's C ABI.
 #include "device_sort.hpp"
 
 extern "C" {

@@ -1,4 +1,4 @@
-"""ctypes binding of tests/cpp/libpst_sort_hooks.so: C forwarders to the sorts and scans of pasture_amd/csrc/device_sort.hpp
+"""ctypes binding of pasture_amd/csrc/build/libpst_sort_hooks.so (source: tests/cpp/sort_hooks.cpp): C forwarders to the sorts and scans of pasture_amd/csrc/device_sort.hpp
 (pstk::radix_sort_pairs_u32 / _u64, sort_pairs_u32 / _u64, radix_sort_first_pass, radix_sort_pairs_supported, exclusive_sum_u32_u64,
 suffix_min_u32).  Test infrastructure: built by `make -C pasture_amd/csrc`, i.e. by __graft_entry__.build(); not part of the C ABI.
 Pointers are plain integers (torch's data_ptr(), 0 = nullptr); `bytes` is a ctypes.c_size_t passed by reference."""
@@ -6,7 +6,7 @@ import ctypes
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "cpp", "libpst_sort_hooks.so")
+LIB_PATH = os.path.join(os.path.dirname(HERE), "pasture_amd", "csrc", "build", "libpst_sort_hooks.so")  # (build products stay out of tests/)
 
 HIP_SUCCESS = 0
 HIP_ERROR_INVALID_VALUE = 1

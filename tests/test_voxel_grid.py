@@ -9,6 +9,7 @@ from pasture_amd._capi import PastureError, PasturePanic
 from pasture_amd.algorithms import voxelgrid_filter
 from pasture_amd.buffers import HashMapBuffer, VectorBuffer
 from pasture_amd.layout import PointLayout, attributes as A
+from voxel_ref import numpy_voxelgrid
 
 COMPLETE = [A.POSITION_3D, A.INTENSITY, A.RETURN_NUMBER, A.NUMBER_OF_RETURNS, A.CLASSIFICATION_FLAGS, A.SCANNER_CHANNEL, A.SCAN_DIRECTION_FLAG,
             A.EDGE_OF_FLIGHT_LINE, A.CLASSIFICATION, A.SCAN_ANGLE_RANK, A.SCAN_ANGLE, A.USER_DATA, A.POINT_SOURCE_ID, A.COLOR_RGB, A.GPS_TIME,
@@ -91,54 +92,6 @@ def test_doc_example(api):
     assert (filtered.view_attribute(A.POSITION_3D)[:, 0] == 0.0).all()
 
 
-def numpy_voxelgrid(rec, layout, leaf):
-    """Independent restatement: nearest-marker cells, sequential sums, deterministic data without most-common ties."""
-    pos = rec[A.POSITION_3D.name()]
-    idx = np.zeros((len(rec), 3), dtype=np.int64)
-    for c in range(3):
-        mn, mx = pos[:, c].min(), pos[:, c].max()
-        markers = []
-        cur = mn
-        while cur < mx:
-            cur += leaf[c]
-            markers.append(cur)
-        markers = np.array(markers)
-        if len(markers):
-            i = np.searchsorted(markers, pos[:, c], side="left")  # first marker >= p
-            prev = markers[np.maximum(i - 1, 0)]
-            back = (i > 0) & (pos[:, c] - prev < markers[i] - pos[:, c])
-            idx[:, c] = i - back
-    order = np.lexsort((np.arange(len(rec)), idx[:, 2], idx[:, 1], idx[:, 0]))
-    keys = idx[order]
-    starts = np.flatnonzero(np.r_[True, (np.diff(keys, axis=0) != 0).any(axis=1)])
-    ends = np.r_[starts[1:], len(rec)]
-    out = np.zeros(len(starts), dtype=layout.numpy_record_dtype())
-    for v, (s, e) in enumerate(zip(starts, ends)):
-        pts = order[s:e]
-        for a in layout.attributes():
-            name = a.name()
-            col = rec[name][pts]
-            if name in ("Position3D", "ColorRGB", "Normal"):
-                acc = np.zeros(3)
-                for row in col.astype(np.float64):
-                    acc = acc + row
-                avg = acc / float(len(pts))
-                out[name][v] = avg if name == "Position3D" else (np.clip(np.trunc(avg), 0, 65535) if name == "ColorRGB" else avg.astype(np.float32))
-            elif name in ("Intensity", "NIR"):
-                acc = 0.0
-                for x in col.astype(np.float64):
-                    acc = acc + x
-                out[name][v] = min(max(int(acc / float(len(pts))), 0), 65535)
-            elif name in ("ClassificationFlags", "GpsTime", "PointID"):
-                out[name][v] = max(0.0, col.astype(np.float64).max())
-            else:
-                vals, counts = np.unique(col, return_counts=True)
-                best = vals[counts == counts.max()]
-                assert len(best) == 1, "test data must not contain most-common ties"
-                out[name][v] = (best[0] != 0) if name in ("ScanDirectionFlag", "EdgeOfFlightLine") else best[0]
-    return out
-
-
 @pytest.mark.parametrize("kinds", [("H", "H"), ("V", "V")])
 # (the last case: 5 000 markers per axis = 13 bits each, a 39-bit voxel key -- the 64-bit-key passes of the library's own radix sort, round 6)
 @pytest.mark.parametrize("n,leaf", [(5000, (2.5, 2.5, 2.5)), (20_000, (6.0, 11.0, 30.0)), (3000, (0.4, 0.4, 50.0)), (6000, (0.004, 0.004, 0.004))])
@@ -196,7 +149,7 @@ def test_random_cloud_matches_numpy(api, kinds, n, leaf):
                 tmp[name][maj] = tmp[name][pts[0]]
     buffer = BUFFER_KINDS[kinds[0]].from_numpy(tmp, layout)
     voxelgrid_filter(buffer, *leaf, filtered)
-    exp = numpy_voxelgrid(tmp, layout, leaf)
+    exp = numpy_voxelgrid(tmp, layout, leaf, forbid_ties=True)
     assert filtered.len() == len(exp)
     for a in layout.attributes():
         got = filtered.view_attribute(a.attribute_definition())
@@ -257,13 +210,13 @@ def test_voxel_reduction_paths_agree(stage):
     """The centroid reduction has two paths per group of 64 voxels -- staged through LDS (the group's points fetched one per lane, sums from LDS)
     and unstaged (one voxel per lane or per wave over global memory) -- chosen by the group's size against a capacity derived from the average
     voxel.  PST_VOXEL_STAGE pins the capacity (0 = never stage, 64 = only groups of single-point voxels, 6144 = the maximum): this file's
-    product cases must pass with every setting (the switch is read once per process, hence the child interpreter)."""
+    and test_voxel_seams.py's product cases (groups of exactly 63 / 64 / 65 and 6143 / 6144 / 6145 points among them) must pass with every setting (the switch is read once per process, hence the child interpreter)."""
     import os
     import subprocess
     import sys
     env = dict(os.environ, PST_VOXEL_STAGE=stage)
     here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_voxel_grid.py"), "-x", "-q", "-m", "gpu", "-k", "not test_voxel_reduction_paths_agree",
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_voxel_grid.py"), os.path.join(here, "test_voxel_seams.py"), "-x", "-q", "-m", "gpu", "-k", "not test_voxel_reduction_paths_agree",
                         "-p", "no:cacheprovider"], env=env, cwd=os.path.dirname(here), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
