@@ -18,14 +18,20 @@
 // Search kernels write ONE aligned 32-byte result record per point at its original index (full-sector stores behind a compute-bound
 // search); split_results_kernel streams the records into the caller's outputs and narrows the normal to the NORMAL attribute (Vec3f32,
 // Rust `as`).
+// Host driver: run_normals is the list of the phases of one call (struct KnnCall): read_bounds, [brute_force,] take_index_arrays, gate_estimate,
+// measure_box, principal_axes, measure_scale, plan_box_search, global_index, first_search (box_search), coarser_levels (all_points), finish.
+// The dense index (keys + sort, reorder, directory) is three launch-only helpers over a DenseIndex view, shared with run_normals_replay; the
+// decisions between the launches are pure functions in normals_plan.hpp.
 // The reference allocates a HashMapBuffer per point and goes through DMatrix; none of that survives: the 3x3 moment
 // sums live in registers.  f64 throughout (sqrt / atan2 / cos / sin from the device math library); -ffp-contract=off.
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "device_sort.hpp"
@@ -964,6 +970,723 @@ struct CallGuard {
   hipStream_t stream;
   ~CallGuard() { (void)hipStreamSynchronize(stream); scratch_cache().end_call(); }  // blocks go back only when nothing in flight uses them
 };
+inline bool ok(hipError_t e) { return e == hipSuccess; }  // the one error convention of the host driver: a phase returns false on a HIP failure
+
+// The device counters of one call: a zeroed 128-byte block.  The kernels take plain pointers to its words; the layout is pinned below.
+struct KnnCounters {
+  unsigned long long n_finite;  // finite points (keys_kernel)
+  unsigned long long n_cells;   // occupied cells (count_cells_kernel: sizes the hash table)
+  uint32_t fb_count;            // queries the box kernel handed back
+  uint32_t pad0[3];
+  int error_count;              // degenerate neighbourhoods
+  uint32_t pad1[7];
+  uint32_t open_count[2];       // queries handed back by the shell cap / by the crowd guard
+  uint32_t collect_count;       // length of the list collect_unresolved_kernel writes
+  uint32_t box_count;           // boxes that hold a query (the census's list, knn_box_list)
+  uint32_t pad2[2];
+  unsigned long long probe[4];  // the probe and census kernels
+  uint32_t pad3[2];
+};
+static_assert(offsetof(KnnCounters, n_finite) == 0 && offsetof(KnnCounters, n_cells) == 8 && offsetof(KnnCounters, fb_count) == 16, "counter layout");
+static_assert(offsetof(KnnCounters, error_count) == 32 && offsetof(KnnCounters, open_count) == 64 && offsetof(KnnCounters, collect_count) == 72, "counter layout");
+static_assert(offsetof(KnnCounters, box_count) == 76 && offsetof(KnnCounters, probe) == 88 && sizeof(KnnCounters) == 128, "counter layout");
+
+// f(std::integral_constant<int, K>) for the smallest instantiated list length K >= k
+template <typename F>
+void with_k(uint32_t k, F&& f) {
+  if (k <= 8) f(std::integral_constant<int, 8>{});
+  else if (k <= 16) f(std::integral_constant<int, 16>{});
+  else if (k <= 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, 64>{});
+}
+template <bool DENSE, bool LIST, typename... Args>
+void launch_grid_search(uint32_t k, unsigned grid, hipStream_t stream, Args... args) {
+  with_k(k, [&](auto K) { hipLaunchKernelGGL((knn_grid_kernel<decltype(K)::value, DENSE, LIST>), dim3(grid), dim3(kBlock), 0, stream, args...); });
+}
+
+// the per-workgroup bounds {mn[3], mx[3]} that gather_positions_kernel and framed_bounds_kernel leave in `partials`, folded on the host
+void fold_bounds(const std::vector<double>& hp, unsigned blocks, double (&mn)[3], double (&mx)[3]) {
+  for (int c = 0; c < 3; ++c) { mn[c] = 1.7976931348623157e308; mx[c] = -mn[c]; }
+  for (unsigned b = 0; b < blocks; ++b)
+    for (int c = 0; c < 3; ++c) { mn[c] = std::fmin(mn[c], hp[b * 6 + c]); mx[c] = std::fmax(mx[c], hp[b * 6 + 3 + c]); }
+}
+
+// The grid of cell edge h (rx fine x cells per h) over the box [mn, mn + bs.ext] in `frame`; returns its number of cells.
+// Points per cell.  With the hash table every cell costs a probe, so few fat cells win: ~k/3 points per cell (the first
+// shell of 27 cells almost always suffices).  With the dense directory a whole row of cells is one range, and small cells win
+// because the searched cube approximates the k-sphere better: ~k/12 points per cell, two shells
+// (global-memory search at k = 16, 10^8 points: 5.33 -> 126 ms, 2.2 -> 116, 1.3 -> 100, 0.8 -> 107, 0.4 -> 145).
+uint64_t grid_for(const double mn[3], const BoxStats& bs, const GridParams& frame, const KnnTuning& tune, double h, uint32_t rx, GridParams& g) {
+  if (tune.cell > 0) h = tune.cell;
+  const double min_h = bs.maxext * (double)rx / 2000000.0;  // <= 2^21 cells per axis
+  if (!(h > min_h)) h = min_h;
+  g.h = h; g.inv_h = 1.0 / h; g.rx = rx; g.hx = h / (double)rx; g.inv_hx = (double)rx / h;
+  g.rotated = frame.rotated;
+  for (int c = 0; c < 9; ++c) g.rot[c] = frame.rot[c];
+  for (int c = 0; c < 3; ++c) g.rot_c[c] = frame.rot_c[c];
+  for (int c = 0; c < 3; ++c) {
+    g.org[c] = mn[c];
+    double d = std::floor(bs.ext[c] * (c == 0 ? g.inv_hx : g.inv_h)) + 1.0;
+    if (d > 2097151.0) d = 2097151.0;
+    g.dim[c] = (uint32_t)d;
+  }
+  return (uint64_t)g.dim[0] * g.dim[1] * g.dim[2];
+}
+
+// ---- the dense index: launches only, over raw pointers -- the synchronous call's cache blocks or a plan's buffers ---------------------------
+struct DenseIndex {
+  uint32_t *keys, *keys2, *idx, *idx2;  // cell numbers and point numbers, before and after the sort
+  double* sorted_xyz;
+  void* tmp;                            // scratch of the sort, then of the suffix minimum, and the bytes the step at hand may use
+  size_t tmp_bytes;
+  uint32_t *directory, *dir_blocks;     // cell_start[cells + 2]; the first point of every block of kDirBlock cells (grids far larger than the cloud)
+  uint64_t n_dblocks;
+};
+// (a) cell numbers -- with the histogram of the sort's first pass where the sort offers that -- and the sort, which numbers the points itself
+bool dense_keys_and_sort(const DenseIndex& v, const double* src, uint64_t cnt, const GridParams& g, unsigned key_bits, unsigned long long* n_finite, unsigned cus,
+                         hipStream_t stream) {
+  RadixFirstPass walk{nullptr, (uint32_t)((cnt + 8191) / 8192), 0, 8192};
+  const RadixFirstPass first = sort_first_pass(v.tmp, cnt, key_bits);
+  if (first.counts) walk = first;
+  hipLaunchKernelGGL(keys_kernel<uint32_t>, dim3(std::max(1u, std::min(walk.tiles, cus * 16u))), dim3(kBlock), 0, stream, src, cnt, g, v.keys, (uint32_t*)nullptr, n_finite, walk);
+  size_t bytes = v.tmp_bytes;
+  return ok(sort_pairs_u32(v.tmp, bytes, v.keys, v.keys2, v.idx, v.idx2, cnt, key_bits, stream, true, &first));
+}
+// (b) the points in sorted order.  One step per workgroup (a grid of cnt / (256 * unroll) workgroups): a plain random gather of 10^8 points
+// measured 2.41 ms that way and 2.58 ms with 2048 workgroups looping (tools/exp_locality.hip)
+void dense_reorder(const DenseIndex& v, const double* src, uint64_t cnt, int unroll, hipStream_t stream) {
+  const int u = unroll >= 4 ? 4 : (unroll == 2 ? 2 : 1);
+  const unsigned rgrid = (unsigned)std::max<uint64_t>(1, (cnt + (uint64_t)kBlock * u - 1) / ((uint64_t)kBlock * u));
+  if (u == 4) hipLaunchKernelGGL(reorder_kernel<4>, dim3(rgrid), dim3(kBlock), 0, stream, src, v.idx2, cnt, v.sorted_xyz);
+  else if (u == 2) hipLaunchKernelGGL(reorder_kernel<2>, dim3(rgrid), dim3(kBlock), 0, stream, src, v.idx2, cnt, v.sorted_xyz);
+  else hipLaunchKernelGGL(reorder_kernel<1>, dim3(rgrid), dim3(kBlock), 0, stream, src, v.idx2, cnt, v.sorted_xyz);
+}
+// (c) cell_start[] from the sorted cell numbers of the nf finite points: block heads, suffix minimum and fill for grids far larger than the cloud
+bool dense_directory(const DenseIndex& v, uint64_t nf, uint64_t cells, unsigned sgrid, hipStream_t stream) {
+  if (cells > 3 * nf) {
+    if (!ok(hipMemsetAsync(v.dir_blocks, 0xFF, v.n_dblocks * 4, stream))) return false;
+    hipLaunchKernelGGL(dir_block_heads_kernel, dim3(sgrid), dim3(kBlock), 0, stream, v.keys2, nf, cells, v.dir_blocks);
+    size_t bytes = v.tmp_bytes;
+    if (!ok(suffix_min_u32(v.tmp, bytes, v.dir_blocks, v.n_dblocks, stream))) return false;
+    hipLaunchKernelGGL(dir_fill_kernel, dim3((unsigned)((v.n_dblocks + kDirPerGroup - 1) / kDirPerGroup)), dim3(kBlock), 0, stream, v.keys2, nf, cells, (const uint32_t*)v.dir_blocks,
+                       v.n_dblocks, v.directory);
+  } else {
+    hipLaunchKernelGGL(build_directory_kernel, dim3(sgrid), dim3(kBlock), 0, stream, v.keys2, nf, cells, v.directory);
+  }
+  return true;
+}
+
+// PST_KNN_TRACE: host wall time of every phase (each mark synchronises the stream)
+struct PhaseTrace {
+  bool on = false;
+  hipStream_t stream = nullptr;
+  std::chrono::steady_clock::time_point t_prev;
+  std::string line;
+  void start() { t_prev = std::chrono::steady_clock::now(); }
+  void mark(const char* what) {
+    if (!on) return;
+    (void)hipStreamSynchronize(stream);
+    const auto now = std::chrono::steady_clock::now();
+    char buf[64];
+    snprintf(buf, sizeof buf, " %s %.1f", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+    line += buf;
+    t_prev = now;
+  }
+};
+
+// One compute_normals call: what its phases share.  run_normals runs the phases in the order they are declared in; every phase returns
+// false on a HIP failure (hipGetLastError has it).
+//
+// What is decided, in this order: is the cloud what its bounding box says (a quick scale estimate against the box's volume)?  The
+// box the grids are laid over (the bounding box; a trimmed one when far points stretch it; the box along the principal axes when the
+// cloud is thin in a direction that is no coordinate axis).  The cell edge h = the radius of the ball that holds M = 1.75 k points --
+// from the box's volume for clouds that fill it, else measured (normals_scale.hip), and checked by a probe of the built index.  Then
+// 1. the LDS box search (normals_tile.hip) over a dense directory with x cells rx times finer than h, when the directory fits its
+//    budget; what it cannot finish goes to 2 as a list;
+// 2. otherwise the global-memory search over the dense directory with ~k/12 points per cubic cell, when the grid is not much larger
+//    than the cloud -- 3. else over Morton keys + a hash table with ~k/3 points per cell;
+// 4. queries 2 / 3 hand back after kShellCap shells: coarser grids over the full bounding box, then an exact search against all points.
+struct KnnCall {
+  static constexpr uint32_t kOpenCap = 1u << 22;  // listed open queries per kind (beyond that the flags are collected in a pass over all points)
+  // inputs
+  hipStream_t stream;
+  uint64_t n;
+  uint32_t k;
+  const KnnTuning& tune = knn_tuning();
+  unsigned cus = 0, sgrid = 1;
+  bool brute = false;   // few points, or no finite one: every point against every point, no index
+  XyzRef xyz{nullptr};  // the packed source: the caller's column, or the staged copy
+  NormalsOut out{};
+  KnnCounters* ctr = nullptr;
+  CacheBuf xyz_own, partials, counters;
+  std::vector<double> hp;  // host copy of `partials`
+  // the box the grids are laid over: the bounding box (full_mn / full_mx), or a trimmed or rotated one; the frame the grids live in: the
+  // cloud's own axes, or its principal axes
+  double mn[3], mx[3], full_mn[3], full_mx[3];
+  GridParams frame{};
+  BoxStats bs{};
+  double occupancy = 0.0;  // fraction of the 32^3 coarse cells of the box that hold a point
+  // scale: points the ball of radius h should hold; the gate's quick estimate; the measured radius and local dimension (clouds that do not fill their box)
+  double m_target = 0.0, h_gate = 0.0, d_gate = 3.0, h_est = 0.0, d_est = 3.0;
+  bool concentrated = false, fills = false;
+  CacheBuf xyz_s;  // a subsample of the cloud (packed xyz; may hold non-finite points): the scale estimate and the bounds of the all-points search
+  uint64_t n_sub = 0;
+  // the spatial index
+  CacheBuf keys, keys2, idx, idx2, sorted_xyz, tmp, rec, directory, dir_blocks, tkeys, tstarts, fb_list;
+  GridParams g{};
+  uint64_t cells = 0, nf = 0;
+  CellTable table{nullptr, nullptr, 0};
+  // the searches
+  TileShape shape;
+  BoxListSink box_sink;
+  bool tiled = false, dense = false;
+  CacheBuf unres, open_lists;  // one byte per point, by ORIGINAL index: the query was handed back by a capped search; and their sorted positions
+  RecOut sorted{};
+  PhaseTrace trace;
+  // what a plan record needs of the box search
+  bool rec_open = false;  // some query was handed back by a capped search (coarser levels / all-points search ran)
+  bool rec_tiled = false, rec_list = false;
+  uint32_t rec_n_list = 0, rec_n_fb = 0;
+
+  KnnCall(hipStream_t s, uint64_t n_, uint32_t k_) : stream(s), n(n_), k(k_) {}
+  void set_box() { bs = BoxStats::of(mn, mx); }
+  uint64_t grid_for(double h, uint32_t rx, GridParams& gp) const { return pstk::grid_for(mn, bs, frame, tune, h, rx, gp); }  // the box and frame of NOW
+  double edge_for(double per_cell) const { return bs.edge_for(per_cell, n); }
+
+  bool read_bounds(const uint8_t* pos_base, uint64_t pos_stride);
+  void brute_force();
+  bool take_index_arrays();
+  bool gate_estimate();
+  bool measure_box();
+  bool principal_axes();
+  bool measure_scale();
+  bool build_index(double h, uint32_t rx, bool dense_dir, const double* src = nullptr, uint64_t cnt = 0);
+  bool build_table();
+  bool plan_box_search();
+  bool global_index();
+  bool first_search();
+  bool box_search(const uint32_t* cell_start);
+  bool all_points(uint8_t which, uint32_t n_q);
+  bool coarser_levels();
+  long long finish(KnnPlanRecord* record);
+};
+
+// stages the source if it is not a packed Vec3f64 array; the bounding box of the finite points; the counters
+bool KnnCall::read_bounds(const uint8_t* pos_base, uint64_t pos_stride) {
+  cus = (unsigned)device_cus();
+  sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)cus * 8));
+  // a packed, 8-byte aligned Vec3f64 array (a HashMapBuffer column, an XYZ-only VectorBuffer) is searched in place: no 24 n-byte copy
+  const bool packed_source = pos_stride == 24 && ((uintptr_t)pos_base & 7u) == 0;
+  if (!packed_source && !ok(xyz_own.alloc(n * 24, stream))) return false;
+  xyz = XyzRef{packed_source ? (const double*)pos_base : (const double*)xyz_own.p};
+  if (!ok(partials.alloc((size_t)sgrid * 48, stream)) || !ok(counters.alloc(sizeof(KnnCounters), stream))) return false;
+  if (!ok(hipMemsetAsync(counters.p, 0, sizeof(KnnCounters), stream))) return false;
+  ctr = counters.as<KnnCounters>();
+  out.error_count = &ctr->error_count;
+  hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, pos_base, pos_stride, n, packed_source ? (double*)nullptr : xyz_own.as<double>(),
+                     partials.as<double>());
+  hp.resize((size_t)sgrid * 6);
+  if (!ok(hipMemcpyAsync(hp.data(), partials.p, hp.size() * 8, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  fold_bounds(hp, sgrid, mn, mx);
+  for (int c = 0; c < 3; ++c) { full_mn[c] = mn[c]; full_mx[c] = mx[c]; }
+  set_box();
+  brute = n <= 2048 || !(mn[0] <= mx[0]);
+  m_target = tune.tau_m > 0 ? tune.tau_m : 1.75 * (double)k;
+  trace.on = tune.trace;
+  trace.stream = stream;
+  return true;
+}
+
+void KnnCall::brute_force() {
+  const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+  with_k(k, [&](auto K) { hipLaunchKernelGGL(knn_bruteforce_kernel<decltype(K)::value>, dim3(grid), dim3(kBlock), 0, stream, xyz.as<double>(), (uint32_t)n, k, out); });
+}
+
+bool KnnCall::take_index_arrays() {
+  trace.start();
+  return ok(keys.alloc(n * 8, stream)) && ok(keys2.alloc(n * 8, stream)) && ok(idx.alloc(n * 4, stream)) && ok(idx2.alloc(n * 4, stream)) && ok(sorted_xyz.alloc(n * 24, stream));
+}
+
+// GATE: is the cloud what its bounding box says?  A quick scale estimate on 2^17 points, 256 queries (normals_scale.hip; 0.3 ms) against the radius
+// the box's volume predicts.  The 32^3 occupancy mask alone is fooled by a thin uniform halo around a dense core (1 % of the points
+// spread over 10^5 times the core's volume fill every coarse cell: the grid was laid for the halo and every cell of the core held
+// 400 000 points -- 32 s for 10^7 points).
+bool KnnCall::gate_estimate() {
+  if (!(n >= 4096 && !tune.forced_scale() && !tune.no_scale)) return true;
+  const uint64_t S = (n + (1u << 17) - 1) >> 17, n_g = n / S;
+  CacheBuf xyz_g, hist_g;
+  if (!ok(xyz_g.alloc(n_g * 24, stream)) || !ok(hist_g.alloc(knn_scale_scratch_bytes(), stream))) return false;
+  hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_g, xyz_g.as<double>(), partials.as<double>());
+  if (knn_scale_estimate(xyz_g.as<double>(), (uint32_t)n_g, (double)S, bs.ext[0] * bs.ext[0] + bs.ext[1] * bs.ext[1] + bs.ext[2] * bs.ext[2], m_target, hist_g.as<unsigned int>(), stream,
+                         h_gate, d_gate, 256)) {
+    const double h_box = edge_for(m_target / kBallVolume);
+    concentrated = cloud_is_concentrated(h_gate, h_box);
+    if (tune.debug) fprintf(stderr, "[pst knn gate] %.1f points within h=%g (dimension %.2f); the box's volume says %g%s\n", m_target, h_gate, d_gate, h_box,
+                            concentrated ? ": concentrated" : "");
+  }
+  trace.mark("gate");
+  return true;
+}
+
+// Fraction of the 32^3 coarse cells of the box that hold a point (flat axes count as one layer), and -- from point counts per slice of
+// every axis, taken in the same pass -- a TRIMMED box: the smallest slice ranges that hold all but 0.05 % of the points at either end,
+// one slice added on each side.  It replaces the bounding box only when it is at least 8 times smaller, i.e. when a few far points
+// stretch the bounding box (64 outliers around 10^7 points: the cloud filled 0.001 % of it, no dense directory fitted, 42 ms instead
+// of 5).  Points outside it are clamped into the boundary cells like the box's own last points; the searches stay exact (a clamped
+// point lies beyond its cell, never nearer), the box kernel hands queries outside the box to the global-memory search.
+bool KnnCall::measure_box() {
+  for (int pass = 0; pass < 4; ++pass) {
+    CacheBuf occ;
+    const size_t occ_bytes = (size_t)kOccWords * 4 + 3 * kAxisBins * 4;
+    if (!ok(occ.alloc(occ_bytes, stream)) || !ok(hipMemsetAsync(occ.p, 0, occ_bytes, stream))) return false;
+    double sc[3], ax[3];
+    for (int c = 0; c < 3; ++c) {
+      sc[c] = bs.ext[c] > bs.maxext * 1e-9 ? (double)kOccBins / bs.ext[c] * (1.0 - 1e-12) : 0.0;
+      ax[c] = bs.ext[c] > bs.maxext * 1e-9 ? (double)kAxisBins / bs.ext[c] * (1.0 - 1e-12) : 0.0;
+    }
+    uint32_t* axis_hist = occ.as<uint32_t>() + kOccWords;
+    const uint64_t S_occ = tune.occupancy_all ? 1 : (n + ((uint64_t)1 << 23) - 1) >> 23;  // (every S-th point: at most 2^23 of them)
+    hipLaunchKernelGGL(occupancy_kernel, dim3(std::min(sgrid, cus * 4)), dim3(kBlock), 0, stream, xyz.as<double>(), n / std::max<uint64_t>(S_occ, 1), std::max<uint64_t>(S_occ, 1), mn[0], mn[1], mn[2], sc[0], sc[1], sc[2],
+                       occ.as<uint32_t>(), ax[0], ax[1], ax[2], axis_hist, frame);
+    std::vector<uint32_t> hb(kOccWords + 3 * kAxisBins);
+    if (!ok(hipMemcpyAsync(hb.data(), occ.p, occ_bytes, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+    uint64_t set = 0;
+    for (uint32_t w = 0; w < kOccWords; ++w) set += (uint64_t)__builtin_popcount(hb[w]);
+    double bins = 1.0;
+    for (int c = 0; c < 3; ++c) bins *= sc[c] > 0 ? (double)kOccBins : 1.0;
+    occupancy = (double)set / bins;
+    if (tune.debug) fprintf(stderr, "[pst knn] occupancy of the box at 32^3: %.3f\n", occupancy);
+    // The trimmed box for a tail mass `cut` (a fraction of the points at either end of every axis).  0.05 % always; for a cloud the gate
+    // found concentrated also 0.5 % and 5 % -- a tenfold cut is taken when it buys at least an eightfold smaller box (a halo).
+    auto trimmed = [&](double cut_frac, double (&tmn)[3], double (&tmx)[3]) { return trimmed_box<kAxisBins>(hb.data() + kOccWords, mn, mx, ax, cut_frac, tmn, tmx); };
+    double tmn[3], tmx[3];
+    double shrink = trimmed(0.0005, tmn, tmx);
+    if (concentrated) {
+      for (double cut_frac : {0.005, 0.05}) {
+        double umn[3], umx[3];
+        const double sh = trimmed(cut_frac, umn, umx);
+        if (sh <= shrink / 8.0) { shrink = sh; for (int c = 0; c < 3; ++c) { tmn[c] = umn[c]; tmx[c] = umx[c]; } }
+        else break;
+      }
+    }
+    // (once a box has been trimmed, the slices are finer and a second and third look may tighten it further: any gain above 40 % is taken)
+    if (!(take_trimmed_box(pass, shrink) && !tune.no_trim)) break;
+    if (tune.debug) fprintf(stderr, "[pst knn] trimmed box: %.3g of the volume: [%g, %g] x [%g, %g] x [%g, %g]\n", shrink, tmn[0], tmx[0], tmn[1], tmx[1], tmn[2], tmx[2]);
+    for (int c = 0; c < 3; ++c) { mn[c] = tmn[c]; mx[c] = tmx[c]; }
+    set_box();
+  }
+  return true;
+}
+
+// PRINCIPAL AXES.  A cloud that is thin along a direction which is not a coordinate axis (a tilted facade, a diagonal flight strip, a
+// helix) fills little of any axis-aligned box: the dense directory over that box would exceed its budget and the search fall back to
+// the hash directory.  The covariance of a subsample (inside the trimmed box) gives the principal axes; if the box in THAT frame is
+// at most a third of the volume, the grid is laid in it: cells, rows and trims use rotated coordinates (grid_frame), distances the
+// original ones.
+bool KnnCall::principal_axes() {
+  if (!consider_rotation(occupancy, n, tune)) return true;
+  const uint64_t S_m = std::max<uint64_t>(1, n >> 20), n_m = n / S_m;
+  CacheBuf sums;
+  if (!ok(sums.alloc(80, stream)) || !ok(hipMemsetAsync(sums.p, 0, 80, stream))) return false;
+  const double ctr_xyz[3] = {0.5 * (mn[0] + mx[0]), 0.5 * (mn[1] + mx[1]), 0.5 * (mn[2] + mx[2])};
+  hipLaunchKernelGGL(moments_kernel, dim3(std::min(sgrid, cus * 4)), dim3(kBlock), 0, stream, xyz.as<double>(), n_m, S_m, mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], ctr_xyz[0],
+                     ctr_xyz[1], ctr_xyz[2], sums.as<double>());
+  double hs[10];
+  if (!ok(hipMemcpyAsync(hs, sums.p, 80, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  if (hs[9] >= 1000.0) {
+    const PrincipalAxes pa = principal_axes_of(hs);
+    GridParams cand{};
+    cand.rotated = 1;
+    for (int c = 0; c < 3; ++c) cand.rot_c[c] = ctr_xyz[c];
+    for (int c = 0; c < 9; ++c) cand.rot[c] = pa.rot[c];
+    if (axes_are_coordinate_axes(pa.align)) { trace.mark("axes"); return true; }  // within 6 degrees: nothing to gain, no pass over the points
+    hipLaunchKernelGGL(framed_bounds_kernel, dim3(sgrid), dim3(kBlock), 0, stream, xyz.as<double>(), n, mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], cand, partials.as<double>());
+    if (!ok(hipMemcpyAsync(hp.data(), partials.p, hp.size() * 8, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+    double rmn[3], rmx[3];
+    fold_bounds(hp, sgrid, rmn, rmx);
+    if (rmn[0] <= rmx[0]) {
+      double v_now = 1.0, v_rot = 1.0;
+      double rext = std::fmax(rmx[0] - rmn[0], std::fmax(rmx[1] - rmn[1], rmx[2] - rmn[2]));
+      for (int c = 0; c < 3; ++c) { v_now *= std::fmax(bs.ext[c], 1e-6 * bs.maxext); v_rot *= std::fmax(rmx[c] - rmn[c], 1e-6 * rext); }
+      if (tune.debug) fprintf(stderr, "[pst knn] principal axes: box %.3g of the axis-aligned one (%g x %g x %g)\n", v_rot / v_now, rmx[0] - rmn[0], rmx[1] - rmn[1], rmx[2] - rmn[2]);
+      if (take_rotated_box(v_rot, v_now)) {
+        frame = cand;
+        for (int c = 0; c < 3; ++c) { mn[c] = rmn[c]; mx[c] = rmx[c]; }
+        set_box();
+        if (!measure_box()) return false;
+      }
+    }
+  }
+  trace.mark("axes");
+  return true;
+}
+
+// The bounding box's volume gives the right h only for clouds that fill it.  For the others (a surface: the first guess is several
+// times too large; separate clusters: orders of magnitude) the scale is MEASURED first, without an index (normals_scale.hip): distance
+// histograms of 512 sampled points against a subsample of 2^20 to 2^22 points give the radius at which the cloud holds M points
+// around a typical point, and its local dimension.
+bool KnnCall::measure_scale() {
+  const double h_box_now = edge_for(m_target / kBallVolume);
+  fills = cloud_fills_box(occupancy, h_gate, h_box_now);  // the cloud is what its (trimmed) box says
+  // (up to 4 million points the gate's subsample is thinned by at most 32 -- as good as the full estimate: taken as it is)
+  const bool gate_enough = gate_is_enough(h_gate, n);
+  if (!fills && gate_enough) { h_est = h_gate; d_est = d_gate; }
+  if (!(!fills && !gate_enough && n >= 4096 && !tune.forced_scale() && !tune.no_scale)) return true;
+  // the subsample: a sixteenth of the cloud, at least 2^18 and at most 2^22 points (the further the thinning, the longer the extrapolation
+  // down to the radius of M points: at 1 in 96 the sheet's h came out 8 % low)
+  const uint64_t cap_s = std::min<uint64_t>(1u << 22, std::max<uint64_t>(1u << 18, n / 16));
+  const uint64_t S = (n + cap_s - 1) / cap_s, n_s = n / S;
+  CacheBuf hist_s;
+  if (!ok(xyz_s.alloc(n_s * 24, stream))) return false;
+  n_sub = n_s;
+  if (!ok(hist_s.alloc(knn_scale_scratch_bytes(), stream))) return false;
+  hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_s, xyz_s.as<double>(),
+                     partials.as<double>());
+  double h_m = 0, dim_m = 3;
+  if (knn_scale_estimate(xyz_s.as<double>(), (uint32_t)n_s, (double)S, bs.ext[0] * bs.ext[0] + bs.ext[1] * bs.ext[1] + bs.ext[2] * bs.ext[2], m_target, hist_s.as<unsigned int>(), stream,
+                         h_m, dim_m)) {
+    if (tune.debug) fprintf(stderr, "[pst knn scale] %llu of %llu points: %.1f points within h=%g, dimension %.2f (by the box's volume: %g)\n", (unsigned long long)n_s,
+                            (unsigned long long)n, m_target, h_m, dim_m, edge_for(m_target / kBallVolume));
+    h_est = h_m; d_est = dim_m;
+  }
+  trace.mark("scale");
+  return true;
+}
+
+// The spatial index for a given grid: keys, radix sort, reorder, and the dense directory or the hash table.
+// (src, cnt): the points to index -- all of them, or a subsample
+bool KnnCall::build_index(double h, uint32_t rx, bool dense_dir, const double* src, uint64_t cnt) {
+  struct Join {  // every way out of this function: the caller's stream waits for what was sent to the side stream
+    hipStream_t stream;
+    SideStream* ss = nullptr;
+    ~Join() { if (ss && hipStreamWaitEvent(stream, ss->join, 0) != hipSuccess) { (void)hipStreamSynchronize(ss->s); } }
+  } join{stream};
+  if (!src) { src = xyz.as<double>(); cnt = n; }
+  cells = grid_for(h, rx, g);
+  g.dense = dense_dir ? 1u : 0u;
+  unsigned key_bits = 64;
+  if (dense_dir) { key_bits = 1; while (key_bits < 32 && (1ull << key_bits) <= cells) ++key_bits; }  // keys 0 .. cells (< 2^32)
+  if (!ok(hipMemsetAsync(&ctr->n_finite, 0, sizeof ctr->n_finite + sizeof ctr->n_cells, stream))) return false;
+  DenseIndex v{keys.as<uint32_t>(), keys2.as<uint32_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), sorted_xyz.as<double>(), nullptr, 0, nullptr, nullptr, 0};
+  if (dense_dir) {
+    // the library's own sort numbers the points itself and takes the histogram of its first pass from the key kernel
+    if (!ok(sort_pairs_u32(nullptr, v.tmp_bytes, v.keys, v.keys2, v.idx, v.idx2, cnt, key_bits, stream)) || !ok(tmp.alloc(v.tmp_bytes, stream))) return false;
+    v.tmp = tmp.p;
+    if (!dense_keys_and_sort(v, src, cnt, g, key_bits, &ctr->n_finite, cus, stream)) return false;
+  } else {
+    const RadixFirstPass walk{nullptr, (uint32_t)((cnt + 8191) / 8192), 0, 8192};
+    hipLaunchKernelGGL(keys_kernel<uint64_t>, dim3(std::max(1u, std::min(walk.tiles, cus * 16u))), dim3(kBlock), 0, stream, src, cnt, g, keys.as<uint64_t>(), idx.as<uint32_t>(), &ctr->n_finite, walk);
+    size_t tmp_bytes = 0;
+    if (!ok(sort_pairs_u64(nullptr, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream))) return false;
+    if (!ok(tmp.alloc(tmp_bytes, stream))) return false;
+    if (!ok(sort_pairs_u64(tmp.p, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream))) return false;
+  }
+  // the reorder: on the side stream, behind the sort; the caller's stream goes on to the directory and waits for the points when this function returns
+  // (unroll, same box, whole kNN call at 10^8 points: 32.6 / 32.3 / 32.4 ms for 1 / 2 / 4)
+  hipStream_t rs = stream;
+  if (tune.side_stream) {
+    SideStream& ss = side_stream();
+    if (ss.ok && hipEventRecord(ss.fork, stream) == hipSuccess && hipStreamWaitEvent(ss.s, ss.fork, 0) == hipSuccess) { rs = ss.s; join.ss = &ss; }
+  }
+  dense_reorder(v, src, cnt, tune.reorder_unroll, rs);
+  if (join.ss && hipEventRecord(join.ss->join, rs) != hipSuccess) { (void)hipStreamSynchronize(rs); join.ss = nullptr; return false; }
+  unsigned long long h_finite = 0;
+  if (!ok(hipMemcpyAsync(&h_finite, &ctr->n_finite, 8, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  nf = h_finite;
+  if (!nf) return true;
+  if (!dense_dir) return build_table();
+  if (!ok(directory.alloc((cells + 2) * 4, stream))) return false;
+  v.directory = directory.as<uint32_t>();
+  if (cells > 3 * nf) {
+    v.n_dblocks = (cells + 1 + kDirBlock - 1) / kDirBlock;
+    if (!ok(dir_blocks.alloc(v.n_dblocks * 4, stream))) return false;
+    v.dir_blocks = dir_blocks.as<uint32_t>();
+    v.tmp_bytes = 0;
+    if (!ok(suffix_min_u32(nullptr, v.tmp_bytes, v.dir_blocks, v.n_dblocks, stream)) || !ok(tmp.alloc(v.tmp_bytes, stream))) return false;
+    v.tmp = tmp.p;
+  }
+  return dense_directory(v, nf, cells, sgrid, stream);
+}
+
+// the hash table of occupied cells over the sorted Morton keys
+bool KnnCall::build_table() {
+  unsigned long long h_cells = 0;
+  hipLaunchKernelGGL(count_cells_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint64_t>(), nf, &ctr->n_cells);
+  if (!ok(hipMemcpyAsync(&h_cells, &ctr->n_cells, 8, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  uint64_t cap = 64;
+  while (cap < 2 * h_cells) cap <<= 1;
+  if (!ok(tkeys.alloc(cap * 8, stream)) || !ok(tstarts.alloc(cap * 4, stream)) || !ok(hipMemsetAsync(tkeys.p, 0xFF, cap * 8, stream))) return false;
+  table = CellTable{tkeys.as<uint64_t>(), tstarts.as<uint32_t>(), (uint32_t)(cap - 1)};
+  hipLaunchKernelGGL(build_table_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint64_t>(), nf, table);
+  return true;
+}
+
+// THE BOX SEARCH's grid: up to three rounds of index, density probe and re-grid; then the census that picks the box shape
+bool KnnCall::plan_box_search() {
+  if (!try_box_search(k, occupancy, n, tune)) return true;
+  // fine x cells per h: 4 for clouds that fill their box; 2 for the others (a surface: the same box holds fewer points, the 31-cell limit of a
+  // box row then makes boxes too short at rx = 4: 6.3 against 3.9 ms per 10^7 points of the sheet in tools/exp_normals_surface.py)
+  uint32_t rx = fine_cells_per_h(h_est, d_est, occupancy, tune);
+  // points per (cubic) cell of edge R0: M = (4/3 pi) R0^3 * density  =>  R0^3 * density = M / (4/3 pi)
+  double h = h_est > 0.0 ? h_est : edge_for(tune.per_cell > 0 ? tune.per_cell : m_target / kBallVolume);
+  for (int round = 0; round < 3; ++round) {
+    GridParams trial{};
+    // (clustered clouds and surfaces leave cells empty: 4 bytes each, up to 20 per point are accepted here)
+    uint64_t trial_cells = grid_for(h, rx, trial);
+    // (default 20 cells per point: 80 bytes per point; 12 left the 10^8-point sheet at rx = 1: 84 against 71 ms)
+    const uint64_t cell_budget = directory_budget(n, tune);
+    while (rx > 1 && !directory_fits(trial_cells, cell_budget)) { rx >>= 1; trial_cells = grid_for(h, rx, trial); }  // coarser x cells before giving up
+    if (!directory_fits(trial_cells, cell_budget)) break;
+    if (!build_index(h, rx, true)) return false;
+    trace.mark("index");
+    if (!nf) break;
+    double m_half = 0, m_full = 0;
+    if (!knn_probe(sorted_xyz.as<double>(), directory.as<uint32_t>(), g, (uint32_t)nf, ctr->probe, stream, m_half, m_full)) return false;
+    // N(r) ~ r^D through (h/2, m_half) and (h, m_full); the radius that holds M points
+    trace.mark("probe");
+    const ProbeFit pf = probe_fit(g.h, m_half, m_full, m_target);
+    const double D = pf.dim, h_new = pf.h_new;
+    if (tune.debug) fprintf(stderr, "[pst knn probe] h=%g: %.1f points within h/2, %.1f within h (target %.1f), dimension %.2f -> h=%g\n", g.h, m_half, m_full, m_target, D, h_new);
+    if (probe_accepts(round, g.h, h_new, tune)) {
+      // (clouds that do not fill their box: the census of the winning shape also lists the boxes that hold a query)
+      box_sink.alloc = [s = stream](size_t bytes) -> uint32_t* { CacheBuf b; return b.alloc(bytes, s) == hipSuccess ? b.as<uint32_t>() : nullptr; };
+      box_sink.count_dev = &ctr->box_count;
+      box_sink.list = nullptr; box_sink.n = 0;
+      box_sink.sorted_cells = keys2.as<uint32_t>();  // (dense grids: 32-bit row-major cell numbers, sorted)
+      tiled = knn_tile_shape(g, nf, cells, k, fills, directory.as<uint32_t>(), ctr->probe, stream, shape, (!fills && tune.box_list) ? &box_sink : nullptr);
+      // Which plane fit the box search runs.  One pass about the query (plane_fit_pivot) agrees with the reference's two passes to a few
+      // ulps of the covariance -- enough wherever the neighbourhood spans three dimensions.  On surfaces and strips the neighbourhoods are
+      // nearly planar, the smallest eigenvalue is the difference of large numbers in the reference's cubic solver, and those ulps become
+      // 1e-8 of the curvature (the deep fuzz: one curvature of 1.4 10^5 on a strip, 1.4e-12 absolute): such clouds keep the reference's
+      // ORDER of operations, which reproduces its rounding.
+      shape.fit_seq = tune.fit >= 0 ? tune.fit == 1 : !fills;
+      trace.mark("census");
+      break;
+    }
+    h = h_new;
+  }
+  return true;
+}
+
+// Without the box search: cubic cells of ~k/12 points (dense directory) or ~k/3 points (hash table) -- by the bounding box's volume, or, where the
+// scale was MEASURED (a cloud that does not fill its box and did not fit the box search's directory budget either), by that: the ball of
+// radius h_est holds M points and N(r) ~ r^D; a cubic cell of edge h holds about what a ball of radius c_D h does (c = 0.62 in 3-D,
+// 0.56 in 2-D, 0.5 in 1-D).  A cloud of dimension D occupies 3^D of the 27 cells of the first shell, so the cell's share is scaled by
+// 3^(3-D): the first shell then holds the same number of candidates whatever the dimension.
+bool KnnCall::global_index() {
+  dense = tiled;
+  if (tiled) return true;
+  const FallbackEdges fe = fallback_edges(bs, n, k, h_est, d_est, m_target, tune);
+  const double h_dense = fe.dense, h_hash = fe.hash;
+  if (tune.debug && h_est > 0.0 && !tune.forced_scale())
+    fprintf(stderr, "[pst knn] measured scale: cell edge %g (dense) / %g (hash) instead of the bounding box's\n", h_dense, h_hash);
+  GridParams trial{};
+  dense = dense_directory_ok(grid_for(h_dense, 1, trial), n);
+  if (tune.dense == 0) dense = false;
+  return build_index(dense ? h_dense : h_hash, 1, dense);
+}
+
+// The first search of every finite point: the box kernel plus what it hands back, or the global-memory search over the dense directory or the hash table.
+// Results go straight into the caller's outputs (default), or as 32-byte records + split_results_kernel (PST_KNN_DIRECT=0: the A/B switch).
+bool KnnCall::first_search() {
+  if (!ok(open_lists.alloc((size_t)2 * kOpenCap * 4, stream)) || !ok(unres.alloc(n, stream)) || !ok(hipMemsetAsync(unres.p, 0, n, stream))) return false;
+  if (!tune.direct_out && !ok(rec.alloc(n * 32, stream))) return false;
+  sorted = RecOut{tune.direct_out ? nullptr : rec.as<double>(), idx2.as<uint32_t>(), out.knn, out.knn_u32, out.error_count,
+                  out.normals_f64, out.curvature_f64, out.normal_attr, out.normal_stride, out.curv_attr, out.curv_stride};
+  if (!nf) return true;
+  if (tiled) return box_search(directory.as<uint32_t>());
+  const unsigned grid = (unsigned)((nf + kBlock - 1) / kBlock);
+  if (dense)
+    launch_grid_search<true, false>(k, grid, stream, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, (const uint32_t*)directory.as<uint32_t>(),
+                                    (const uint32_t*)nullptr, (uint32_t)nf, sorted, kShellCap, unres.as<uint8_t>(), ctr->open_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
+  else
+    launch_grid_search<false, false>(k, grid, stream, sorted_xyz.as<double>(), (const uint64_t*)keys2.as<uint64_t>(), (uint32_t)nf, k, g, table,
+                                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)nf, sorted, kShellCap, unres.as<uint8_t>(), ctr->open_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
+  return true;
+}
+
+// box kernel first; what it hands back (k-th distance beyond tau0, ambiguous packed keys, boxes denser than its LDS budget) goes to
+// the global-memory search as a list
+bool KnnCall::box_search(const uint32_t* cell_start) {
+  if (!ok(fb_list.alloc(nf * 4, stream)) || !ok(hipMemsetAsync(&ctr->fb_count, 0, 4, stream))) return false;
+  // clouds that do not fill their box launch one workgroup per box that holds a query (a sheet leaves two thirds of them empty)
+  CacheBuf box_list;
+  uint32_t n_list = 0;
+  const uint32_t* list_ptr = nullptr;
+  if (!fills && tune.box_list && box_sink.list) {
+    list_ptr = box_sink.list;
+    n_list = box_sink.n;
+    if (tune.debug) fprintf(stderr, "[pst knn] %u of %u boxes hold a query (listed by the census)\n", n_list, knn_box_count(shape, g));
+  } else if (!fills && tune.box_list) {
+    if (!ok(box_list.alloc((size_t)knn_box_count(shape, g) * 4, stream))) return false;
+    n_list = knn_box_list(shape, cell_start, g, box_list.as<uint32_t>(), &ctr->box_count, stream);
+    if (n_list == 0xFFFFFFFFu) return false;
+    list_ptr = box_list.as<uint32_t>();
+    if (tune.debug) fprintf(stderr, "[pst knn] %u of %u boxes hold a query\n", n_list, knn_box_count(shape, g));
+    trace.mark("box-list");
+  }
+  launch_knn_tile(shape, sorted_xyz.as<double>(), cell_start, g, k, (uint32_t)nf, sorted, fb_list.as<uint32_t>(), &ctr->fb_count, list_ptr, n_list, stream);
+  uint32_t n_fb = 0;
+  if (!ok(hipMemcpyAsync(&n_fb, &ctr->fb_count, 4, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  rec_tiled = true; rec_list = list_ptr != nullptr; rec_n_list = n_list; rec_n_fb = n_fb;
+  trace.mark("box-search");
+  if (tune.debug)
+    fprintf(stderr, "[pst knn] fit=%s n=%llu nf=%llu cells=%llu dim=%ux%ux%u h=%g box=%ux%ux%u kernel=%c threads=%u cap=%u fallback=%u\n", shape.fit_seq ? "reference-order" : "one-pass+guard", (unsigned long long)n,
+            (unsigned long long)nf, (unsigned long long)cells, g.dim[0], g.dim[1], g.dim[2], g.h, shape.bx, shape.by, shape.bz, shape.tag, shape.threads,
+            shape.cap, n_fb);
+  if (!n_fb) return true;
+  // The box kernel appends its leftovers in the order its workgroups finish: 64 consecutive entries come from 64 different boxes.
+  // Sorted by position (= by cell) the lanes of a wave search neighbouring cells and share their candidates' cache lines
+  // (PST_KNN_SORT_FALLBACK=0: the A/B switch; same box, 10^8 points: uniform cloud 32.9 -> 32.45 ms, but the sheet 45.0 -> 46.2 --
+  // volume-like clouds only).  The unsorted key / index buffers of the index build are free by now.
+  const uint32_t* fb_q = fb_list.as<uint32_t>();
+  if (tune.sort_fallback && fills && n_fb >= 4096) {
+    uint32_t *ka = fb_list.as<uint32_t>(), *kb = keys.as<uint32_t>(), *va = keys.as<uint32_t>() + n, *vb = idx.as<uint32_t>();
+    unsigned bits = 1;
+    while (bits < 32 && (1ull << bits) <= nf) ++bits;
+    size_t sb = 0;
+    // (only the sorted keys are used: iota = true lets the first scatter number the values instead of reading `va`, which is uninitialised scratch)
+    if (!ok(sort_pairs_u32(nullptr, sb, ka, kb, va, vb, n_fb, bits, stream, true)) || !ok(tmp.alloc(sb, stream))) return false;
+    if (!ok(sort_pairs_u32(tmp.p, sb, ka, kb, va, vb, n_fb, bits, stream, true))) return false;
+    fb_q = kb;
+  }
+  launch_grid_search<true, true>(k, (unsigned)((n_fb + kBlock - 1) / kBlock), stream, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, cell_start,
+                                 fb_q, n_fb, sorted, kShellCap, unres.as<uint8_t>(), ctr->open_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
+  return true;
+}
+
+// The exact search of n_q open queries (flag `which`) against all points by a workgroup each: bound / filter / select
+bool KnnCall::all_points(uint8_t which, uint32_t n_q) {
+  const uint32_t* open_q = nullptr;
+  if (n_q <= kOpenCap) {
+    // the search that flagged them listed their sorted positions (same index: nothing was re-sorted in between): no pass over all points
+    open_q = open_lists.as<uint32_t>() + (which == 2 ? kOpenCap : 0u);
+    hipLaunchKernelGGL(clear_flags_kernel, dim3((n_q + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, open_q, n_q, (const uint32_t*)idx2.as<uint32_t>(), unres.as<uint8_t>());
+  } else {
+    if (!ok(fb_list.alloc((size_t)nf * 4, stream)) || !ok(hipMemsetAsync(&ctr->collect_count, 0, 4, stream))) return false;
+    hipLaunchKernelGGL(collect_unresolved_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const uint32_t*)idx2.as<uint32_t>(), (uint32_t)nf,
+                       unres.as<uint8_t>(), which, fb_list.as<uint32_t>(), &ctr->collect_count);
+    open_q = fb_list.as<uint32_t>();
+  }
+  if (tune.debug) fprintf(stderr, "[pst knn] %u open queries against all %llu points\n", n_q, (unsigned long long)nf);
+  if (!n_sub) {  // (clouds that fill their box had no scale estimate: take the subsample now)
+    const uint64_t cap_s = std::min<uint64_t>(1u << 22, std::max<uint64_t>(1u << 20, n / 16));
+    const uint64_t S = (n + cap_s - 1) / cap_s;
+    n_sub = n / S;
+    if (!ok(xyz_s.alloc(n_sub * 24, stream))) return false;
+    hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_sub, xyz_s.as<double>(),
+                       partials.as<double>());
+  }
+  const uint32_t cand_cap = 4096, batch = 16384;  // (16 KB of candidate list per open query: 256 MB per batch)
+  CacheBuf bound, cand_count, cand, qpack;
+  const uint32_t n_b = std::min(n_q, batch);
+  if (!ok(bound.alloc((size_t)n_b * 8, stream)) || !ok(qpack.alloc((size_t)n_b * 32, stream)) || !ok(cand_count.alloc((size_t)n_b * 4, stream))) return false;
+  if (!ok(cand.alloc((size_t)n_b * cand_cap * 4, stream))) return false;
+  for (uint32_t off = 0; off < n_q; off += batch) {
+    const uint32_t cnt = std::min(batch, n_q - off);
+    const uint32_t* ql = open_q + off;
+    if (!ok(hipMemsetAsync(cand_count.p, 0, (size_t)cnt * 4, stream))) return false;
+    // (the first quarter of the subsample -- itself a uniform thinning, in input order -- is enough for the bound: four times the
+    // candidates per query, which the culled filter and the select kernel barely notice, for a quarter of the scan)
+    const uint32_t n_bound = (uint32_t)std::max<uint64_t>(n_sub / 4, std::min<uint64_t>(n_sub, 1u << 18));
+    with_k(k, [&](auto K) {
+      hipLaunchKernelGGL(knn_bound_kernel<decltype(K)::value>, dim3(cnt), dim3(kBlock), 0, stream, sorted_xyz.as<double>(), ql, cnt, (const double*)xyz_s.as<double>(), n_bound, k, bound.as<double>());
+    });
+    hipLaunchKernelGGL(knn_pack_queries_kernel, dim3((cnt + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const double*)sorted_xyz.as<double>(), ql, cnt,
+                       (const double*)bound.as<double>(), qpack.as<double>());
+    hipLaunchKernelGGL(knn_filter_kernel, dim3((unsigned)((nf + kBlock * kFilterPts - 1) / (kBlock * kFilterPts))), dim3(kBlock), 0, stream,
+                       (const double*)sorted_xyz.as<double>(), (uint32_t)nf, (const double*)qpack.as<double>(), cnt, cand_cap, cand_count.as<uint32_t>(),
+                       cand.as<uint32_t>());
+    with_k(k, [&](auto K) {
+      hipLaunchKernelGGL(knn_select_kernel<decltype(K)::value>, dim3(cnt), dim3(kBlock), 0, stream, sorted_xyz.as<double>(), (uint32_t)nf, k, ql, cnt, (const uint32_t*)cand_count.as<uint32_t>(),
+                         (const uint32_t*)cand.as<uint32_t>(), cand_cap, sorted);
+    });
+  }
+  trace.mark("all-points");
+  return true;
+}
+
+// Queries a capped search handed back (flag 1: outliers; regions far sparser than the grid was made for): again on a grid with six
+// times the cell edge, laid over the FULL bounding box (the trimmed or rotated box of the first level clamps exactly the points these
+// queries are made of) -- its first shell covers what six shells of the last one did.  On such a grid a cell over a dense part of
+// the cloud holds millions of points and a grid search walks a cell with ONE lane: a query that meets a range of more than kCrowd
+// points gives up (flag 2) and is searched exactly against all points by a workgroup (all_points), as are the
+// last few open ones, whose all-points search costs less than another index.
+bool KnnCall::coarser_levels() {
+  for (int level = 1; nf; ++level) {
+    uint32_t n_open[2] = {0, 0};  // handed back by the shell cap / by the crowd guard
+    if (!ok(hipMemcpyAsync(n_open, ctr->open_count, 8, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+    if (!ok(hipMemsetAsync(ctr->open_count, 0, sizeof ctr->open_count, stream))) return false;
+    if (n_open[0] || n_open[1]) rec_open = true;
+    if (n_open[1] && !all_points(2, n_open[1])) return false;
+    const uint32_t n_un = n_open[0];
+    if (!n_un) break;
+    if (level == 1) {  // from here on: the cloud's own axes and its full bounding box
+      frame = GridParams{};
+      for (int c = 0; c < 3; ++c) { mn[c] = full_mn[c]; mx[c] = full_mx[c]; }
+      set_box();
+    }
+    const double h_up = g.h * (double)kShellCap;
+    GridParams trial{};
+    const uint64_t up_cells = grid_for(h_up, 1, trial);
+    const bool last = std::max(trial.dim[0], std::max(trial.dim[1], trial.dim[2])) <= (uint32_t)kShellCap + 1u;
+    const bool up_dense = dense_directory_ok(up_cells, n);
+    // all points or another level?  The all-points search does ~2e12 pairs per second; an index costs ~2 ns per point with a dense
+    // directory and ~4.5 ns with the hash table (64-bit Morton keys, eight radix passes, the table), and may leave queries open.
+    if (search_all_points(level, n_un, nf, up_dense)) return all_points(1, n_un);
+    if (tune.debug) fprintf(stderr, "[pst knn] level %d: %u open queries, cell edge %g (%s)%s\n", level, n_un, h_up, up_dense ? "dense" : "hash", last ? ", uncapped" : "");
+    if (!build_index(h_up, 1, up_dense)) return false;
+    if (!ok(fb_list.alloc((size_t)nf * 4, stream)) || !ok(hipMemsetAsync(&ctr->collect_count, 0, 4, stream))) return false;
+    hipLaunchKernelGGL(collect_unresolved_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const uint32_t*)idx2.as<uint32_t>(), (uint32_t)nf,
+                       unres.as<uint8_t>(), (uint8_t)1, fb_list.as<uint32_t>(), &ctr->collect_count);
+    const unsigned grid = (unsigned)((n_un + kBlock - 1) / kBlock);
+    const int cap = last ? 0 : kShellCap;
+    if (up_dense)
+      launch_grid_search<true, true>(k, grid, stream, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, (const uint32_t*)directory.as<uint32_t>(),
+                                     (const uint32_t*)fb_list.as<uint32_t>(), n_un, sorted, cap, unres.as<uint8_t>(), ctr->open_count, kCrowd, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
+    else
+      launch_grid_search<false, true>(k, grid, stream, sorted_xyz.as<double>(), (const uint64_t*)keys2.as<uint64_t>(), (uint32_t)nf, k, g, table, (const uint32_t*)nullptr,
+                                      (const uint32_t*)fb_list.as<uint32_t>(), n_un, sorted, cap, unres.as<uint8_t>(), ctr->open_count, kCrowd, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
+    trace.mark("coarser");
+  }
+  return true;
+}
+
+// The non-finite points, the split of the records, the count of degenerate neighbourhoods, and what a plan needs to run the call again.
+// Returns what run_normals returns.
+long long KnnCall::finish(KnnPlanRecord* record) {
+  if (!brute) {
+    if (nf < n) {
+      // non-finite query points: every distance is NaN (-> +inf), so "the k nearest" is the reference's kd-tree tie order
+      // (unpinned).  Chosen here: the point itself, then the first k-1 finite points in sorted order.
+      const unsigned grid = (unsigned)((n - nf + kBlock - 1) / kBlock);
+      hipLaunchKernelGGL(knn_nonfinite_kernel, dim3(grid), dim3(kBlock), 0, stream, xyz.as<double>(), sorted_xyz.as<double>(), (uint32_t)nf, (uint32_t)n, k,
+                         sorted);
+    }
+    trace.mark("fallback");
+    if (!tune.direct_out) {
+      hipLaunchKernelGGL(split_results_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const double*)rec.as<double>(), n, out);
+      trace.mark("split");
+    }
+    if (trace.on) fprintf(stderr, "[pst knn trace]%s\n", trace.line.c_str());
+  }
+  int errors = 0;
+  if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(&errors, out.error_count, 4, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return -1;
+  if (record && rec_tiled) {  // (a valid record had no open query: no index was built after the box search, g / cells / nf / shape are still its own)
+    if (rec_open) record->why_not = "some queries were handed back by a capped search (far points, sparse regions): the coarser levels are host-driven";
+    else if (nf != n) record->why_not = "the cloud holds non-finite points";
+    else if (!tune.direct_out) record->why_not = "PST_KNN_DIRECT=0";
+    else if (out.knn) record->why_not = "int64 neighbour lists are a host-side format";
+    else {
+      record->valid = true; record->why_not = "";
+      record->n = n; record->nf = nf; record->cells = cells; record->k = k; record->g = g; record->shape = shape;
+      record->use_list = rec_list; record->n_list = rec_n_list; record->n_fb = rec_n_fb;
+      unsigned kb = 1; while (kb < 32 && (1ull << kb) <= cells) ++kb;
+      record->key_bits = kb;
+    }
+  }
+  return errors;
+}
 }  // namespace
 
 // Frees the device blocks the calling thread's kNN calls keep between calls (about 55 bytes per point of the largest recent cloud, capped at PST_SCRATCH_MAX_BYTES, default 16 GiB).
@@ -974,663 +1697,21 @@ void release_normals_scratch() { scratch_cache().release_all(); }  // (the curre
 long long run_normals(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, double* out_normals_dev, double* out_curv_dev,
                       long long* out_knn_dev, uint32_t* out_knn_u32_dev, uint64_t normal_attr, uint64_t normal_stride, uint64_t curv_attr,
                       uint64_t curv_stride, hipStream_t stream, KnnPlanRecord* record) {
-#define NCK(x) do { if ((x) != hipSuccess) return -1; } while (0)
   if (record) { *record = KnnPlanRecord{}; record->why_not = "the call did not take the LDS box search"; }
-  bool rec_open = false;         // some query was handed back by a capped search (coarser levels / all-points search ran)
-  bool rec_tiled = false, rec_list = false;
-  uint32_t rec_n_list = 0, rec_n_fb = 0;
-  TileShape rec_shape{};
-  GridParams rec_g{};
-  uint64_t rec_cells = 0, rec_nf = 0;
   if (n >= 0xFFFFFFF0ull) return -2;  // sorted indices and directory entries are uint32_t
-  const unsigned cus = (unsigned)device_cus();
-  const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)cus * 8));
-  // a packed, 8-byte aligned Vec3f64 array (a HashMapBuffer column, an XYZ-only VectorBuffer) is searched in place: no 24 n-byte copy
-  const bool packed_source = pos_stride == 24 && ((uintptr_t)pos_base & 7u) == 0;
   CallGuard scratch_guard{stream};  // every exit of this function hands the scratch blocks back to the cache (all of them synchronise the stream or fail)
-  CacheBuf xyz_own, partials, counters;
-  if (!packed_source) NCK(xyz_own.alloc(n * 24, stream));
-  XyzRef xyz{packed_source ? (const double*)pos_base : (const double*)xyz_own.p};
-  NCK(partials.alloc((size_t)sgrid * 48, stream));
-  NCK(counters.alloc(128, stream));
-  NCK(hipMemsetAsync(counters.p, 0, 128, stream));
-  hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, pos_base, pos_stride, n, packed_source ? (double*)nullptr : xyz_own.as<double>(),
-                     partials.as<double>());
-  std::vector<double> hp((size_t)sgrid * 6);
-  NCK(hipMemcpyAsync(hp.data(), partials.p, hp.size() * 8, hipMemcpyDeviceToHost, stream));
-  NCK(hipStreamSynchronize(stream));
-  double mn[3] = {1.7976931348623157e308, 1.7976931348623157e308, 1.7976931348623157e308}, mx[3] = {-mn[0], -mn[0], -mn[0]};
-  for (unsigned b = 0; b < sgrid; ++b)
-    for (int c = 0; c < 3; ++c) { mn[c] = std::fmin(mn[c], hp[b * 6 + c]); mx[c] = std::fmax(mx[c], hp[b * 6 + 3 + c]); }
-
-  NormalsOut out{};
-  out.normals_f64 = out_normals_dev; out.curvature_f64 = out_curv_dev; out.knn = out_knn_dev; out.knn_u32 = out_knn_u32_dev;
-  out.normal_attr = normal_attr; out.normal_stride = normal_stride; out.curv_attr = curv_attr; out.curv_stride = curv_stride;
-  unsigned long long* n_finite = (unsigned long long*)counters.p;
-  unsigned long long* n_cells = n_finite + 1;
-  uint32_t* fb_count = (uint32_t*)((uint8_t*)counters.p + 16);
-  out.error_count = (int*)((uint8_t*)counters.p + 32);
-
-  const bool any_finite = mn[0] <= mx[0];
-  const bool brute = n <= 2048 || !any_finite;
-#define KNN_DISPATCH_T(GRID, K1, K2, K3, K4, ...)                                                       \
-  do {                                                                                                  \
-    if (k <= 8) hipLaunchKernelGGL((K1), dim3(GRID), dim3(kBlock), 0, stream, __VA_ARGS__);            \
-    else if (k <= 16) hipLaunchKernelGGL((K2), dim3(GRID), dim3(kBlock), 0, stream, __VA_ARGS__);      \
-    else if (k <= 32) hipLaunchKernelGGL((K3), dim3(GRID), dim3(kBlock), 0, stream, __VA_ARGS__);      \
-    else hipLaunchKernelGGL((K4), dim3(GRID), dim3(kBlock), 0, stream, __VA_ARGS__);                   \
-  } while (0)
-#define KNN_DISPATCH(KERNEL, GRID, ...) KNN_DISPATCH_T(GRID, KERNEL<8>, KERNEL<16>, KERNEL<32>, KERNEL<64>, __VA_ARGS__)
-#define KNN_DISPATCH_GRID(DENSE, LIST, GRID, ...)                                                                                          \
-  KNN_DISPATCH_T(GRID, (knn_grid_kernel<8, DENSE, LIST>), (knn_grid_kernel<16, DENSE, LIST>), (knn_grid_kernel<32, DENSE, LIST>),          \
-                 (knn_grid_kernel<64, DENSE, LIST>), __VA_ARGS__)
-  if (brute) {
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    KNN_DISPATCH(knn_bruteforce_kernel, grid, xyz.as<double>(), (uint32_t)n, k, out);
+  KnnCall call(stream, n, k);
+  call.out.normals_f64 = out_normals_dev; call.out.curvature_f64 = out_curv_dev; call.out.knn = out_knn_dev; call.out.knn_u32 = out_knn_u32_dev;
+  call.out.normal_attr = normal_attr; call.out.normal_stride = normal_stride; call.out.curv_attr = curv_attr; call.out.curv_stride = curv_stride;
+  if (!call.read_bounds(pos_base, pos_stride)) return -1;
+  if (call.brute) {
+    call.brute_force();
   } else {
-    // cell edge: a sphere of radius h should hold about k points  =>  (4/3 pi) h^3 * density ~ k
-    GridParams frame{};  // the frame the grids live in: the cloud's own axes, or (below) its principal axes
-    const double full_mn[3] = {mn[0], mn[1], mn[2]}, full_mx[3] = {mx[0], mx[1], mx[2]};  // the bounding box (mn / mx may become a trimmed or rotated one)
-    // the box the grids are laid over: the bounding box, or (below) a trimmed one when a few far points stretch it
-    const KnnTuning& tune = knn_tuning();
-    BoxStats bs{};
-    double (&ext)[3] = bs.ext;
-    double& maxext = bs.maxext;
-    auto set_box = [&]() { bs = BoxStats::of(mn, mx); };
-    set_box();
-    // Points per cell.  With the hash table every cell costs a probe, so few fat cells win: ~k/3 points per cell (the first
-    // shell of 27 cells almost always suffices).  With the dense directory a whole row of cells is one range, and small cells win
-    // because the searched cube approximates the k-sphere better: ~k/12 points per cell, two shells
-    // (global-memory search at k = 16, 10^8 points: 5.33 -> 126 ms, 2.2 -> 116, 1.3 -> 100, 0.8 -> 107, 0.4 -> 145).
-    auto grid_for = [&](double h, uint32_t rx, GridParams& g) -> uint64_t {
-      if (tune.cell > 0) h = tune.cell;
-      const double min_h = maxext * (double)rx / 2000000.0;  // <= 2^21 cells per axis
-      if (!(h > min_h)) h = min_h;
-      g.h = h; g.inv_h = 1.0 / h; g.rx = rx; g.hx = h / (double)rx; g.inv_hx = (double)rx / h;
-      g.rotated = frame.rotated;
-      for (int c = 0; c < 9; ++c) g.rot[c] = frame.rot[c];
-      for (int c = 0; c < 3; ++c) g.rot_c[c] = frame.rot_c[c];
-      for (int c = 0; c < 3; ++c) {
-        g.org[c] = mn[c];
-        double d = std::floor(ext[c] * (c == 0 ? g.inv_hx : g.inv_h)) + 1.0;
-        if (d > 2097151.0) d = 2097151.0;
-        g.dim[c] = (uint32_t)d;
-      }
-      return (uint64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    };
-    auto edge_for = [&](double per_cell) { return bs.edge_for(per_cell, n); };
-    auto is_dense = [&](uint64_t cells) { return dense_directory_ok(cells, n); };
-    const double per_cell_env = tune.per_cell;
-    const bool debug = tune.debug;
-    const bool trace = tune.trace;  // host wall time of every phase (each mark synchronises the stream)
-    auto t_prev = std::chrono::steady_clock::now();
-    std::string trace_line;
-    auto mark = [&](const char* what) {
-      if (!trace) return;
-      (void)hipStreamSynchronize(stream);
-      const auto now = std::chrono::steady_clock::now();
-      char buf[64];
-      snprintf(buf, sizeof buf, " %s %.1f", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-      trace_line += buf;
-      t_prev = now;
-    };
-
-    CacheBuf keys, keys2, idx, idx2, sorted_xyz, tmp, rec, directory, dir_blocks, tkeys, tstarts, fb_list;
-    NCK(keys.alloc(n * 8, stream)); NCK(keys2.alloc(n * 8, stream)); NCK(idx.alloc(n * 4, stream)); NCK(idx2.alloc(n * 4, stream));
-    NCK(sorted_xyz.alloc(n * 24, stream));
-    GridParams g{};
-    uint64_t cells = 0, nf = 0;
-    CellTable table{nullptr, nullptr, 0};
-    // The spatial index for a given grid: keys, radix sort, reorder, and the dense directory or the hash table.  Returns false on a HIP failure.
-    // (src, cnt): the points to index -- all of them, or the subsample the density estimate below works on
-    auto build_index = [&](double h, uint32_t rx, bool dense, const double* src = nullptr, uint64_t cnt = 0) -> bool {
-#define BCK(x) do { if ((x) != hipSuccess) return false; } while (0)
-      struct Join {  // every way out of this function: the caller's stream waits for what was sent to the side stream
-        hipStream_t stream;
-        SideStream* ss = nullptr;
-        ~Join() { if (ss && hipStreamWaitEvent(stream, ss->join, 0) != hipSuccess) { (void)hipStreamSynchronize(ss->s); } }
-      } join{stream};
-      if (!src) { src = xyz.as<double>(); cnt = n; }
-      cells = grid_for(h, rx, g);
-      g.dense = dense ? 1u : 0u;
-      unsigned key_bits = 64;
-      if (dense) { key_bits = 1; while (key_bits < 32 && (1ull << key_bits) <= cells) ++key_bits; }  // keys 0 .. cells (< 2^32)
-      BCK(hipMemsetAsync(counters.p, 0, 16, stream));
-      size_t tmp_bytes = 0;
-      pstk::RadixFirstPass walk{nullptr, (uint32_t)((cnt + 8191) / 8192), 0, 8192};
-      if (dense) {
-        // the library's own sort numbers the points itself and takes the histogram of its first pass from the key kernel
-        BCK(sort_pairs_u32(nullptr, tmp_bytes, keys.as<uint32_t>(), keys2.as<uint32_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream));
-        BCK(tmp.alloc(tmp_bytes, stream));
-        const pstk::RadixFirstPass first = pstk::sort_first_pass(tmp.p, cnt, key_bits);
-        if (first.counts) walk = first;
-        hipLaunchKernelGGL(keys_kernel<uint32_t>, dim3(std::max(1u, std::min(walk.tiles, cus * 16u))), dim3(kBlock), 0, stream, src, cnt, g, keys.as<uint32_t>(), (uint32_t*)nullptr, n_finite, walk);
-        BCK(sort_pairs_u32(tmp.p, tmp_bytes, keys.as<uint32_t>(), keys2.as<uint32_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream, true, &first));
-      } else {
-        hipLaunchKernelGGL(keys_kernel<uint64_t>, dim3(std::max(1u, std::min(walk.tiles, cus * 16u))), dim3(kBlock), 0, stream, src, cnt, g, keys.as<uint64_t>(), idx.as<uint32_t>(), n_finite, walk);
-        BCK(sort_pairs_u64(nullptr, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream));
-        BCK(tmp.alloc(tmp_bytes, stream));
-        BCK(sort_pairs_u64(tmp.p, tmp_bytes, keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), cnt, key_bits, stream));
-      }
-      {
-        const int unroll = tune.reorder_unroll;  // (same box, whole kNN call at 10^8 points: 32.6 / 32.3 / 32.4 ms for 1 / 2 / 4)
-        // one step per workgroup (a grid of cnt / (256 * unroll) workgroups): a plain random gather of 10^8 points measured 2.41 ms that way and
-        // 2.58 ms with 2048 workgroups looping (tools/exp_locality.hip)
-        const int u = unroll >= 4 ? 4 : (unroll == 2 ? 2 : 1);
-        const unsigned rgrid = (unsigned)std::max<uint64_t>(1, (cnt + (uint64_t)kBlock * u - 1) / ((uint64_t)kBlock * u));
-        // on the side stream, behind the sort; the caller's stream goes on to the directory and waits for the points when this function returns
-        hipStream_t rs = stream;
-        if (tune.side_stream) {
-          SideStream& ss = side_stream();
-          if (ss.ok && hipEventRecord(ss.fork, stream) == hipSuccess && hipStreamWaitEvent(ss.s, ss.fork, 0) == hipSuccess) { rs = ss.s; join.ss = &ss; }
-        }
-        if (u == 4) hipLaunchKernelGGL(reorder_kernel<4>, dim3(rgrid), dim3(kBlock), 0, rs, src, idx2.as<uint32_t>(), cnt, sorted_xyz.as<double>());
-        else if (u == 2) hipLaunchKernelGGL(reorder_kernel<2>, dim3(rgrid), dim3(kBlock), 0, rs, src, idx2.as<uint32_t>(), cnt, sorted_xyz.as<double>());
-        else hipLaunchKernelGGL(reorder_kernel<1>, dim3(rgrid), dim3(kBlock), 0, rs, src, idx2.as<uint32_t>(), cnt, sorted_xyz.as<double>());
-        if (join.ss && hipEventRecord(join.ss->join, rs) != hipSuccess) { (void)hipStreamSynchronize(rs); join.ss = nullptr; return false; }
-      }
-      unsigned long long h_counts[2] = {0, 0};
-      BCK(hipMemcpyAsync(&h_counts[0], n_finite, 8, hipMemcpyDeviceToHost, stream));
-      BCK(hipStreamSynchronize(stream));
-      nf = h_counts[0];
-      if (!nf) return true;
-      if (dense) {
-        BCK(directory.alloc((cells + 2) * 4, stream));
-        if (cells > 3 * nf) {
-          const uint64_t n_dblocks = (cells + 1 + kDirBlock - 1) / kDirBlock;
-          BCK(dir_blocks.alloc(n_dblocks * 4, stream));
-          BCK(hipMemsetAsync(dir_blocks.p, 0xFF, n_dblocks * 4, stream));
-          hipLaunchKernelGGL(dir_block_heads_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint32_t>(), nf, cells, dir_blocks.as<uint32_t>());
-          size_t sb = 0;
-          BCK(suffix_min_u32(nullptr, sb, dir_blocks.as<uint32_t>(), n_dblocks, stream));
-          BCK(tmp.alloc(sb, stream));
-          BCK(suffix_min_u32(tmp.p, sb, dir_blocks.as<uint32_t>(), n_dblocks, stream));
-          hipLaunchKernelGGL(dir_fill_kernel, dim3((unsigned)((n_dblocks + kDirPerGroup - 1) / kDirPerGroup)), dim3(kBlock), 0, stream, keys2.as<uint32_t>(), nf, cells, (const uint32_t*)dir_blocks.as<uint32_t>(),
-                             n_dblocks, directory.as<uint32_t>());
-        } else {
-          hipLaunchKernelGGL(build_directory_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint32_t>(), nf, cells, directory.as<uint32_t>());
-        }
-      } else {
-        hipLaunchKernelGGL(count_cells_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint64_t>(), nf, n_cells);
-        BCK(hipMemcpyAsync(&h_counts[1], n_cells, 8, hipMemcpyDeviceToHost, stream));
-        BCK(hipStreamSynchronize(stream));
-        uint64_t cap = 64;
-        while (cap < 2 * h_counts[1]) cap <<= 1;
-        BCK(tkeys.alloc(cap * 8, stream)); BCK(tstarts.alloc(cap * 4, stream));
-        BCK(hipMemsetAsync(tkeys.p, 0xFF, cap * 8, stream));
-        table = CellTable{tkeys.as<uint64_t>(), tstarts.as<uint32_t>(), (uint32_t)(cap - 1)};
-        hipLaunchKernelGGL(build_table_kernel, dim3(sgrid), dim3(kBlock), 0, stream, keys2.as<uint64_t>(), nf, table);
-      }
-      return true;
-#undef BCK
-    };
-
-    // What is decided here, in this order: is the cloud what its bounding box says (a quick scale estimate against the box's volume)?  The
-    // box the grids are laid over (the bounding box; a trimmed one when far points stretch it; the box along the principal axes when the
-    // cloud is thin in a direction that is no coordinate axis).  The cell edge h = the radius of the ball that holds M = 1.75 k points --
-    // from the box's volume for clouds that fill it, else measured (normals_scale.hip), and checked by a probe of the built index.  Then
-    // 1. the LDS box search (normals_tile.hip) over a dense directory with x cells rx times finer than h, when the directory fits its
-    //    budget; what it cannot finish goes to 2 as a list;
-    // 2. otherwise the global-memory search over the dense directory with ~k/12 points per cubic cell, when the grid is not much larger
-    //    than the cloud -- 3. else over Morton keys + a hash table with ~k/3 points per cell;
-    // 4. queries 2 / 3 hand back after kShellCap shells: coarser grids over the full bounding box, then an exact search against all points.
-    TileShape shape;
-    BoxListSink box_sink;
-    bool tiled = false;
-    double h_est = 0.0, d_est = 3.0;  // measured (clouds that do not fill their box): the radius holding M = 1.75 k points, the local dimension
-    unsigned long long* scratch3 = (unsigned long long*)((uint8_t*)counters.p + 88);  // four counters of the probe / census kernels (88 .. 120)
-    double m_target = 1.75 * (double)k;  // points the ball of radius h should hold
-    if (tune.tau_m > 0) m_target = tune.tau_m;
-    // GATE: is the cloud what its bounding box says?  A quick scale estimate on 2^17 points, 256 queries (normals_scale.hip; 0.3 ms) against the radius
-    // the box's volume predicts.  The 32^3 occupancy mask alone is fooled by a thin uniform halo around a dense core (1 % of the points
-    // spread over 10^5 times the core's volume fill every coarse cell: the grid was laid for the halo and every cell of the core held
-    // 400 000 points -- 32 s for 10^7 points).
-    double h_gate = 0.0, d_gate = 3.0;
-    bool concentrated = false;
-    if (n >= 4096 && !tune.forced_scale() && !tune.no_scale) {
-      const uint64_t S = (n + (1u << 17) - 1) >> 17, n_g = n / S;
-      CacheBuf xyz_g, hist_g;
-      NCK(xyz_g.alloc(n_g * 24, stream));
-      NCK(hist_g.alloc(knn_scale_scratch_bytes(), stream));
-      hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_g, xyz_g.as<double>(), partials.as<double>());
-      if (knn_scale_estimate(xyz_g.as<double>(), (uint32_t)n_g, (double)S, ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2], m_target, hist_g.as<unsigned int>(), stream,
-                             h_gate, d_gate, 256)) {
-        const double h_box = edge_for(m_target / kBallVolume);
-        concentrated = cloud_is_concentrated(h_gate, h_box);
-        if (debug) fprintf(stderr, "[pst knn gate] %.1f points within h=%g (dimension %.2f); the box's volume says %g%s\n", m_target, h_gate, d_gate, h_box,
-                           concentrated ? ": concentrated" : "");
-      }
-      mark("gate");
-    }
-    // fraction of the 32^3 coarse cells of the box that hold a point (flat axes count as one layer), and -- from point counts per slice of
-    // every axis, taken in the same pass -- a TRIMMED box: the smallest slice ranges that hold all but 0.05 % of the points at either end,
-    // one slice added on each side.  It replaces the bounding box only when it is at least 8 times smaller, i.e. when a few far points
-    // stretch the bounding box (64 outliers around 10^7 points: the cloud filled 0.001 % of it, no dense directory fitted, 42 ms instead
-    // of 5).  Points outside it are clamped into the boundary cells like the box's own last points; the searches stay exact (a clamped
-    // point lies beyond its cell, never nearer), the box kernel hands queries outside the box to the global-memory search.
-    double occupancy = 0.0;
-    auto measure_box = [&]() -> bool {
-#define MCK(x) do { if ((x) != hipSuccess) return false; } while (0)
-    for (int pass = 0; pass < 4; ++pass) {
-      CacheBuf occ;
-      const size_t occ_bytes = (size_t)kOccWords * 4 + 3 * kAxisBins * 4;
-      MCK(occ.alloc(occ_bytes, stream));
-      MCK(hipMemsetAsync(occ.p, 0, occ_bytes, stream));
-      double sc[3], ax[3];
-      for (int c = 0; c < 3; ++c) {
-        sc[c] = ext[c] > maxext * 1e-9 ? (double)kOccBins / ext[c] * (1.0 - 1e-12) : 0.0;
-        ax[c] = ext[c] > maxext * 1e-9 ? (double)kAxisBins / ext[c] * (1.0 - 1e-12) : 0.0;
-      }
-      uint32_t* axis_hist = occ.as<uint32_t>() + kOccWords;
-      const uint64_t S_occ = tune.occupancy_all ? 1 : (n + ((uint64_t)1 << 23) - 1) >> 23;  // (every S-th point: at most 2^23 of them)
-      hipLaunchKernelGGL(occupancy_kernel, dim3(std::min(sgrid, cus * 4)), dim3(kBlock), 0, stream, xyz.as<double>(), n / std::max<uint64_t>(S_occ, 1), std::max<uint64_t>(S_occ, 1), mn[0], mn[1], mn[2], sc[0], sc[1], sc[2],
-                         occ.as<uint32_t>(), ax[0], ax[1], ax[2], axis_hist, frame);
-      std::vector<uint32_t> hb(kOccWords + 3 * kAxisBins);
-      MCK(hipMemcpyAsync(hb.data(), occ.p, occ_bytes, hipMemcpyDeviceToHost, stream));
-      MCK(hipStreamSynchronize(stream));
-      uint64_t set = 0;
-      for (uint32_t w = 0; w < kOccWords; ++w) set += (uint64_t)__builtin_popcount(hb[w]);
-      double bins = 1.0;
-      for (int c = 0; c < 3; ++c) bins *= sc[c] > 0 ? (double)kOccBins : 1.0;
-      occupancy = (double)set / bins;
-      if (debug) fprintf(stderr, "[pst knn] occupancy of the box at 32^3: %.3f\n", occupancy);
-      // The trimmed box for a tail mass `cut` (a fraction of the points at either end of every axis).  0.05 % always; for a cloud the gate
-      // found concentrated also 0.5 % and 5 % -- a tenfold cut is taken when it buys at least an eightfold smaller box (a halo).
-      auto trimmed = [&](double cut_frac, double (&tmn)[3], double (&tmx)[3]) { return trimmed_box<kAxisBins>(hb.data() + kOccWords, mn, mx, ax, cut_frac, tmn, tmx); };
-      double tmn[3], tmx[3];
-      double shrink = trimmed(0.0005, tmn, tmx);
-      if (concentrated) {
-        for (double cut_frac : {0.005, 0.05}) {
-          double umn[3], umx[3];
-          const double sh = trimmed(cut_frac, umn, umx);
-          if (sh <= shrink / 8.0) { shrink = sh; for (int c = 0; c < 3; ++c) { tmn[c] = umn[c]; tmx[c] = umx[c]; } }
-          else break;
-        }
-      }
-      // (once a box has been trimmed, the slices are finer and a second and third look may tighten it further: any gain above 40 % is taken)
-      if (take_trimmed_box(pass, shrink) && !tune.no_trim) {
-        if (debug) fprintf(stderr, "[pst knn] trimmed box: %.3g of the volume: [%g, %g] x [%g, %g] x [%g, %g]\n", shrink, tmn[0], tmx[0], tmn[1], tmx[1], tmn[2], tmx[2]);
-        for (int c = 0; c < 3; ++c) { mn[c] = tmn[c]; mx[c] = tmx[c]; }
-        set_box();
-        continue;
-      }
-      break;
-    }
-    return true;
-#undef MCK
-    };
-    if (!measure_box()) return -1;
-    mark("occupancy");
-    // PRINCIPAL AXES.  A cloud that is thin along a direction which is not a coordinate axis (a tilted facade, a diagonal flight strip, a
-    // helix) fills little of any axis-aligned box: the dense directory over that box would exceed its budget and the search fall back to
-    // the hash directory.  The covariance of a subsample (inside the trimmed box) gives the principal axes; if the box in THAT frame is
-    // at most a third of the volume, the grid is laid in it: cells, rows and trims use rotated coordinates (grid_frame), distances the
-    // original ones.
-    if (consider_rotation(occupancy, n, tune)) {
-      const uint64_t S_m = std::max<uint64_t>(1, n >> 20), n_m = n / S_m;
-      CacheBuf sums;
-      NCK(sums.alloc(80, stream));
-      NCK(hipMemsetAsync(sums.p, 0, 80, stream));
-      const double ctr[3] = {0.5 * (mn[0] + mx[0]), 0.5 * (mn[1] + mx[1]), 0.5 * (mn[2] + mx[2])};
-      hipLaunchKernelGGL(moments_kernel, dim3(std::min(sgrid, cus * 4)), dim3(kBlock), 0, stream, xyz.as<double>(), n_m, S_m, mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], ctr[0],
-                         ctr[1], ctr[2], sums.as<double>());
-      double hs[10];
-      NCK(hipMemcpyAsync(hs, sums.p, 80, hipMemcpyDeviceToHost, stream));
-      NCK(hipStreamSynchronize(stream));
-      if (hs[9] >= 1000.0) {
-        const double c = hs[9], m0 = hs[0] / c, m1 = hs[1] / c, m2 = hs[2] / c;
-        double A[3][3] = {{hs[3] / c - m0 * m0, hs[4] / c - m0 * m1, hs[5] / c - m0 * m2}, {0, hs[6] / c - m1 * m1, hs[7] / c - m1 * m2}, {0, 0, hs[8] / c - m2 * m2}};
-        A[1][0] = A[0][1]; A[2][0] = A[0][2]; A[2][1] = A[1][2];
-        double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};  // columns = eigenvectors (cyclic Jacobi)
-        for (int sweep = 0; sweep < 30; ++sweep) {
-          const double off = std::fabs(A[0][1]) + std::fabs(A[0][2]) + std::fabs(A[1][2]);
-          if (!(off > 1e-300) || off < 1e-14 * (std::fabs(A[0][0]) + std::fabs(A[1][1]) + std::fabs(A[2][2]))) break;
-          for (int pi = 0; pi < 2; ++pi)
-            for (int qi = pi + 1; qi < 3; ++qi) {
-              if (A[pi][qi] == 0.0) continue;
-              const double theta = (A[qi][qi] - A[pi][pi]) / (2.0 * A[pi][qi]);
-              const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0)), cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-              for (int r = 0; r < 3; ++r) { const double arp = A[r][pi], arq = A[r][qi]; A[r][pi] = cs * arp - sn * arq; A[r][qi] = sn * arp + cs * arq; }
-              for (int r = 0; r < 3; ++r) { const double apr = A[pi][r], aqr = A[qi][r]; A[pi][r] = cs * apr - sn * aqr; A[qi][r] = sn * apr + cs * aqr; }
-              for (int r = 0; r < 3; ++r) { const double vrp = V[r][pi], vrq = V[r][qi]; V[r][pi] = cs * vrp - sn * vrq; V[r][qi] = sn * vrp + cs * vrq; }
-            }
-        }
-        int order[3] = {0, 1, 2};  // largest variance first: the grid's rows (x) run along the cloud's longest direction
-        std::sort(order, order + 3, [&](int a, int b) { return A[a][a] > A[b][b]; });
-        GridParams cand{};
-        cand.rotated = 1;
-        for (int cc = 0; cc < 3; ++cc) cand.rot_c[cc] = ctr[cc];
-        for (int r = 0; r < 3; ++r)
-          for (int cc = 0; cc < 3; ++cc) cand.rot[3 * r + cc] = V[cc][order[r]];
-        double align = 1.0;  // the smallest of the rows' largest components: 1 = the principal axes ARE the coordinate axes (in some order)
-        for (int r = 0; r < 3; ++r) align = std::fmin(align, std::fmax(std::fabs(cand.rot[3 * r]), std::fmax(std::fabs(cand.rot[3 * r + 1]), std::fabs(cand.rot[3 * r + 2]))));
-        if (axes_are_coordinate_axes(align)) { mark("axes"); goto axes_done; }  // within 6 degrees: nothing to gain, no pass over the points
-        hipLaunchKernelGGL(framed_bounds_kernel, dim3(sgrid), dim3(kBlock), 0, stream, xyz.as<double>(), n, mn[0], mn[1], mn[2], mx[0], mx[1], mx[2], cand, partials.as<double>());
-        NCK(hipMemcpyAsync(hp.data(), partials.p, hp.size() * 8, hipMemcpyDeviceToHost, stream));
-        NCK(hipStreamSynchronize(stream));
-        double rmn[3] = {1.7976931348623157e308, 1.7976931348623157e308, 1.7976931348623157e308}, rmx[3] = {-rmn[0], -rmn[0], -rmn[0]};
-        for (unsigned b = 0; b < sgrid; ++b)
-          for (int cc = 0; cc < 3; ++cc) { rmn[cc] = std::fmin(rmn[cc], hp[b * 6 + cc]); rmx[cc] = std::fmax(rmx[cc], hp[b * 6 + 3 + cc]); }
-        if (rmn[0] <= rmx[0]) {
-          double v_now = 1.0, v_rot = 1.0;
-          double rext = std::fmax(rmx[0] - rmn[0], std::fmax(rmx[1] - rmn[1], rmx[2] - rmn[2]));
-          for (int cc = 0; cc < 3; ++cc) { v_now *= std::fmax(ext[cc], 1e-6 * maxext); v_rot *= std::fmax(rmx[cc] - rmn[cc], 1e-6 * rext); }
-          if (debug) fprintf(stderr, "[pst knn] principal axes: box %.3g of the axis-aligned one (%g x %g x %g)\n", v_rot / v_now, rmx[0] - rmn[0], rmx[1] - rmn[1], rmx[2] - rmn[2]);
-          if (take_rotated_box(v_rot, v_now)) {
-            frame = cand;
-            for (int cc = 0; cc < 3; ++cc) { mn[cc] = rmn[cc]; mx[cc] = rmx[cc]; }
-            set_box();
-            if (!measure_box()) return -1;
-          }
-        }
-      }
-      mark("axes");
-    }
-    axes_done:;
-    CacheBuf xyz_s;  // a subsample of the cloud (packed xyz; may hold non-finite points): the scale estimate and the bounds of the all-points search
-    uint64_t n_sub = 0;
-    // The bounding box's volume gives the right h only for clouds that fill it.  For the others (a surface: the first guess is several
-    // times too large; separate clusters: orders of magnitude) the scale is MEASURED first, without an index (normals_scale.hip): distance
-    // histograms of 512 sampled points against a subsample of 2^20 to 2^22 points give the radius at which the cloud holds M points
-    // around a typical point, and its local dimension.
-    const double h_box_now = edge_for(m_target / kBallVolume);
-    const bool fills = cloud_fills_box(occupancy, h_gate, h_box_now);  // the cloud is what its (trimmed) box says
-    // (up to 4 million points the gate's subsample is thinned by at most 32 -- as good as the full estimate: taken as it is)
-    const bool gate_enough = gate_is_enough(h_gate, n);
-    if (!fills && gate_enough) { h_est = h_gate; d_est = d_gate; }
-    if (!fills && !gate_enough && n >= 4096 && !tune.forced_scale() && !tune.no_scale) {
-      // the subsample: a sixteenth of the cloud, at least 2^18 and at most 2^22 points (the further the thinning, the longer the extrapolation
-      // down to the radius of M points: at 1 in 96 the sheet's h came out 8 % low)
-      const uint64_t cap_s = std::min<uint64_t>(1u << 22, std::max<uint64_t>(1u << 18, n / 16));
-      const uint64_t S = (n + cap_s - 1) / cap_s, n_s = n / S;
-      CacheBuf hist_s;
-      NCK(xyz_s.alloc(n_s * 24, stream));
-      n_sub = n_s;
-      NCK(hist_s.alloc(knn_scale_scratch_bytes(), stream));
-      hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_s, xyz_s.as<double>(),
-                         partials.as<double>());
-      double h_m = 0, dim_m = 3;
-      if (knn_scale_estimate(xyz_s.as<double>(), (uint32_t)n_s, (double)S, ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2], m_target, hist_s.as<unsigned int>(), stream,
-                             h_m, dim_m)) {
-        if (debug) fprintf(stderr, "[pst knn scale] %llu of %llu points: %.1f points within h=%g, dimension %.2f (by the box's volume: %g)\n", (unsigned long long)n_s,
-                           (unsigned long long)n, m_target, h_m, dim_m, edge_for(m_target / kBallVolume));
-        h_est = h_m; d_est = dim_m;
-      }
-      mark("scale");
-    }
-    if (try_box_search(k, occupancy, n, tune)) {
-      // fine x cells per h: 4 for clouds that fill their box; 2 for the others (a surface: the same box holds fewer points, the 31-cell limit of a
-      // box row then makes boxes too short at rx = 4: 6.3 against 3.9 ms per 10^7 points of the sheet in tools/exp_normals_surface.py)
-      uint32_t rx = fine_cells_per_h(h_est, d_est, occupancy, tune);
-      // points per (cubic) cell of edge R0: M = (4/3 pi) R0^3 * density  =>  R0^3 * density = M / (4/3 pi)
-      double h = h_est > 0.0 ? h_est : edge_for(per_cell_env > 0 ? per_cell_env : m_target / kBallVolume);
-      for (int round = 0; round < 3; ++round) {
-        GridParams trial{};
-        // (clustered clouds and surfaces leave cells empty: 4 bytes each, up to 20 per point are accepted here)
-        uint64_t trial_cells = grid_for(h, rx, trial);
-        // (default 20 cells per point: 80 bytes per point; 12 left the 10^8-point sheet at rx = 1: 84 against 71 ms)
-        const uint64_t cell_budget = directory_budget(n, tune);
-        while (rx > 1 && !directory_fits(trial_cells, cell_budget)) { rx >>= 1; trial_cells = grid_for(h, rx, trial); }  // coarser x cells before giving up
-        if (!directory_fits(trial_cells, cell_budget)) break;
-        if (!build_index(h, rx, true)) return -1;
-        mark("index");
-        if (!nf) break;
-        double m_half = 0, m_full = 0;
-        if (!knn_probe(sorted_xyz.as<double>(), directory.as<uint32_t>(), g, (uint32_t)nf, scratch3, stream, m_half, m_full)) return -1;
-        // N(r) ~ r^D through (h/2, m_half) and (h, m_full); the radius that holds M points
-        mark("probe");
-        const ProbeFit pf = probe_fit(g.h, m_half, m_full, m_target);
-        const double D = pf.dim, h_new = pf.h_new;
-        if (debug) fprintf(stderr, "[pst knn probe] h=%g: %.1f points within h/2, %.1f within h (target %.1f), dimension %.2f -> h=%g\n", g.h, m_half, m_full, m_target, D, h_new);
-        if (probe_accepts(round, g.h, h_new, tune)) {
-          // (clouds that do not fill their box: the census of the winning shape also lists the boxes that hold a query)
-          box_sink.alloc = [&](size_t bytes) -> uint32_t* { CacheBuf b; return b.alloc(bytes, stream) == hipSuccess ? b.as<uint32_t>() : nullptr; };
-          box_sink.count_dev = (uint32_t*)((uint8_t*)counters.p + 76);
-          box_sink.list = nullptr; box_sink.n = 0;
-          box_sink.sorted_cells = keys2.as<uint32_t>();  // (dense grids: 32-bit row-major cell numbers, sorted)
-          tiled = knn_tile_shape(g, nf, cells, k, fills, directory.as<uint32_t>(), scratch3, stream, shape, (!fills && tune.box_list) ? &box_sink : nullptr);
-          // Which plane fit the box search runs.  One pass about the query (plane_fit_pivot) agrees with the reference's two passes to a few
-          // ulps of the covariance -- enough wherever the neighbourhood spans three dimensions.  On surfaces and strips the neighbourhoods are
-          // nearly planar, the smallest eigenvalue is the difference of large numbers in the reference's cubic solver, and those ulps become
-          // 1e-8 of the curvature (the deep fuzz: one curvature of 1.4 10^5 on a strip, 1.4e-12 absolute): such clouds keep the reference's
-          // ORDER of operations, which reproduces its rounding.
-          shape.fit_seq = tune.fit >= 0 ? tune.fit == 1 : !fills;
-          mark("census");
-          break;
-        }
-        h = h_new;
-      }
-    }
-    bool dense = tiled;
-    if (!tiled) {
-      // Cubic cells of ~k/12 points (dense directory) or ~k/3 points (hash table) -- by the bounding box's volume, or, where the scale was
-      // MEASURED above (a cloud that does not fill its box and did not fit the box search's directory budget either), by that: the ball of
-      // radius h_est holds M points and N(r) ~ r^D; a cubic cell of edge h holds about what a ball of radius c_D h does (c = 0.62 in 3-D,
-      // 0.56 in 2-D, 0.5 in 1-D).  A cloud of dimension D occupies 3^D of the 27 cells of the first shell, so the cell's share is scaled by
-      // 3^(3-D): the first shell then holds the same number of candidates whatever the dimension.
-      const FallbackEdges fe = fallback_edges(bs, n, k, h_est, d_est, m_target, tune);
-      const double h_dense = fe.dense, h_hash = fe.hash;
-      if (debug && h_est > 0.0 && !tune.forced_scale())
-        fprintf(stderr, "[pst knn] measured scale: cell edge %g (dense) / %g (hash) instead of the bounding box's\n", h_dense, h_hash);
-      GridParams trial{};
-      dense = is_dense(grid_for(h_dense, 1, trial));
-      if (tune.dense == 0) dense = false;
-      if (!build_index(dense ? h_dense : h_hash, 1, dense)) return -1;
-    }
-    CacheBuf unres, open_lists;  // one byte per point, by ORIGINAL index: the query was handed back by a capped search; and their sorted positions
-    constexpr uint32_t kOpenCap = 1u << 22;  // listed open queries per kind (beyond that the flags are collected in a pass over all points)
-    NCK(open_lists.alloc((size_t)2 * kOpenCap * 4, stream));
-    NCK(unres.alloc(n, stream));
-    NCK(hipMemsetAsync(unres.p, 0, n, stream));
-    uint32_t* unres_count = (uint32_t*)((uint8_t*)counters.p + 64);
-    // results: straight into the caller's outputs (default), or as 32-byte records + split_results_kernel (PST_KNN_DIRECT=0: the A/B switch)
-    const bool direct_out = tune.direct_out;
-    if (!direct_out) NCK(rec.alloc(n * 32, stream));
-    RecOut sorted{direct_out ? nullptr : rec.as<double>(), idx2.as<uint32_t>(), out.knn, out.knn_u32, out.error_count,
-                  out.normals_f64, out.curvature_f64, out.normal_attr, out.normal_stride, out.curv_attr, out.curv_stride};
-    if (nf) {
-      if (dense) {
-        const uint32_t* cell_start = directory.as<uint32_t>();
-        if (tiled) {
-          // box kernel first; what it hands back (k-th distance beyond tau0, ambiguous packed keys, boxes denser than its LDS budget) goes to
-          // the global-memory search as a list
-          NCK(fb_list.alloc(nf * 4, stream));
-          NCK(hipMemsetAsync(fb_count, 0, 4, stream));
-          // clouds that do not fill their box launch one workgroup per box that holds a query (a sheet leaves two thirds of them empty)
-          CacheBuf box_list;
-          uint32_t n_list = 0;
-          const uint32_t* list_ptr = nullptr;
-          if (!fills && tune.box_list && box_sink.list) {
-            list_ptr = box_sink.list;
-            n_list = box_sink.n;
-            if (debug) fprintf(stderr, "[pst knn] %u of %u boxes hold a query (listed by the census)\n", n_list, knn_box_count(shape, g));
-          } else if (!fills && tune.box_list) {
-            NCK(box_list.alloc((size_t)knn_box_count(shape, g) * 4, stream));
-            n_list = knn_box_list(shape, cell_start, g, box_list.as<uint32_t>(), unres_count + 3, stream);
-            if (n_list == 0xFFFFFFFFu) return -1;
-            list_ptr = box_list.as<uint32_t>();
-            if (debug) fprintf(stderr, "[pst knn] %u of %u boxes hold a query\n", n_list, knn_box_count(shape, g));
-            mark("box-list");
-          }
-          launch_knn_tile(shape, sorted_xyz.as<double>(), cell_start, g, k, (uint32_t)nf, sorted, fb_list.as<uint32_t>(), fb_count, list_ptr, n_list, stream);
-          uint32_t n_fb = 0;
-          NCK(hipMemcpyAsync(&n_fb, fb_count, 4, hipMemcpyDeviceToHost, stream));
-          NCK(hipStreamSynchronize(stream));
-          rec_tiled = true; rec_list = list_ptr != nullptr; rec_n_list = n_list; rec_n_fb = n_fb; rec_shape = shape; rec_g = g; rec_cells = cells; rec_nf = nf;
-          mark("box-search");
-          if (debug)
-            fprintf(stderr, "[pst knn] fit=%s n=%llu nf=%llu cells=%llu dim=%ux%ux%u h=%g box=%ux%ux%u kernel=%c threads=%u cap=%u fallback=%u\n", shape.fit_seq ? "reference-order" : "one-pass+guard", (unsigned long long)n,
-                    (unsigned long long)nf, (unsigned long long)cells, g.dim[0], g.dim[1], g.dim[2], g.h, shape.bx, shape.by, shape.bz, shape.tag, shape.threads,
-                    shape.cap, n_fb);
-          if (n_fb) {
-            // The box kernel appends its leftovers in the order its workgroups finish: 64 consecutive entries come from 64 different boxes.
-            // Sorted by position (= by cell) the lanes of a wave search neighbouring cells and share their candidates' cache lines
-            // (PST_KNN_SORT_FALLBACK=0: the A/B switch; same box, 10^8 points: uniform cloud 32.9 -> 32.45 ms, but the sheet 45.0 -> 46.2 --
-            // volume-like clouds only).  The unsorted key / index buffers of the index build are free by now.
-            const uint32_t* fb_q = fb_list.as<uint32_t>();
-            const bool sort_fb = tune.sort_fallback;
-            if (sort_fb && fills && n_fb >= 4096) {
-              uint32_t *ka = fb_list.as<uint32_t>(), *kb = keys.as<uint32_t>(), *va = keys.as<uint32_t>() + n, *vb = idx.as<uint32_t>();
-              unsigned bits = 1;
-              while (bits < 32 && (1ull << bits) <= nf) ++bits;
-              size_t sb = 0;
-              // (only the sorted keys are used: iota = true lets the first scatter number the values instead of reading `va`, which is uninitialised scratch)
-              NCK(sort_pairs_u32(nullptr, sb, ka, kb, va, vb, n_fb, bits, stream, true));
-              NCK(tmp.alloc(sb, stream));
-              NCK(sort_pairs_u32(tmp.p, sb, ka, kb, va, vb, n_fb, bits, stream, true));
-              fb_q = kb;
-            }
-            const unsigned grid = (unsigned)((n_fb + kBlock - 1) / kBlock);
-            KNN_DISPATCH_GRID(true, true, grid, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, cell_start,
-                              fb_q, n_fb, sorted, kShellCap, unres.as<uint8_t>(), unres_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
-          }
-        } else {
-          const unsigned grid = (unsigned)((nf + kBlock - 1) / kBlock);
-          KNN_DISPATCH_GRID(true, false, grid, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, cell_start,
-                            (const uint32_t*)nullptr, (uint32_t)nf, sorted, kShellCap, unres.as<uint8_t>(), unres_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
-        }
-      } else {
-        const unsigned grid = (unsigned)((nf + kBlock - 1) / kBlock);
-        KNN_DISPATCH_GRID(false, false, grid, sorted_xyz.as<double>(), (const uint64_t*)keys2.as<uint64_t>(), (uint32_t)nf, k, g, table,
-                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)nf, sorted, kShellCap, unres.as<uint8_t>(), unres_count, 0u, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
-      }
-      // Queries a capped search handed back (flag 1: outliers; regions far sparser than the grid was made for): again on a grid with six
-      // times the cell edge, laid over the FULL bounding box (the trimmed or rotated box of the first level clamps exactly the points these
-      // queries are made of) -- its first shell covers what six shells of the last one did.  On such a grid a cell over a dense part of
-      // the cloud holds millions of points and a grid search walks a cell with ONE lane: a query that meets a range of more than kCrowd
-      // points gives up (flag 2) and is searched exactly against all points by a workgroup (bound / filter / select above), as are the
-      // last few open ones, whose all-points search costs less than another index.
-      auto all_points = [&](uint8_t which, uint32_t n_q) -> bool {
-#define ACK(x) do { if ((x) != hipSuccess) return false; } while (0)
-        const uint32_t* open_q = nullptr;
-        if (n_q <= kOpenCap) {
-          // the search that flagged them listed their sorted positions (same index: nothing was re-sorted in between): no pass over all points
-          open_q = open_lists.as<uint32_t>() + (which == 2 ? kOpenCap : 0u);
-          hipLaunchKernelGGL(clear_flags_kernel, dim3((n_q + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, open_q, n_q, (const uint32_t*)idx2.as<uint32_t>(), unres.as<uint8_t>());
-        } else {
-          ACK(fb_list.alloc((size_t)nf * 4, stream));
-          ACK(hipMemsetAsync(unres_count + 2, 0, 4, stream));
-          hipLaunchKernelGGL(collect_unresolved_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const uint32_t*)idx2.as<uint32_t>(), (uint32_t)nf,
-                             unres.as<uint8_t>(), which, fb_list.as<uint32_t>(), unres_count + 2);
-          open_q = fb_list.as<uint32_t>();
-        }
-        if (debug) fprintf(stderr, "[pst knn] %u open queries against all %llu points\n", n_q, (unsigned long long)nf);
-        if (!n_sub) {  // (clouds that fill their box had no scale estimate: take the subsample now)
-          const uint64_t cap_s = std::min<uint64_t>(1u << 22, std::max<uint64_t>(1u << 20, n / 16));
-          const uint64_t S = (n + cap_s - 1) / cap_s;
-          n_sub = n / S;
-          ACK(xyz_s.alloc(n_sub * 24, stream));
-          hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const uint8_t*)xyz.as<double>(), 24 * S, n_sub, xyz_s.as<double>(),
-                             partials.as<double>());
-        }
-        const uint32_t cand_cap = 4096, batch = 16384;  // (16 KB of candidate list per open query: 256 MB per batch)
-        CacheBuf bound, cand_count, cand, qpack;
-        const uint32_t n_b = std::min(n_q, batch);
-        ACK(bound.alloc((size_t)n_b * 8, stream));
-        ACK(qpack.alloc((size_t)n_b * 32, stream));
-        ACK(cand_count.alloc((size_t)n_b * 4, stream));
-        ACK(cand.alloc((size_t)n_b * cand_cap * 4, stream));
-        for (uint32_t off = 0; off < n_q; off += batch) {
-          const uint32_t cnt = std::min(batch, n_q - off);
-          const uint32_t* ql = open_q + off;
-          ACK(hipMemsetAsync(cand_count.p, 0, (size_t)cnt * 4, stream));
-          // (the first quarter of the subsample -- itself a uniform thinning, in input order -- is enough for the bound: four times the
-          // candidates per query, which the culled filter and the select kernel barely notice, for a quarter of the scan)
-          const uint32_t n_bound = (uint32_t)std::max<uint64_t>(n_sub / 4, std::min<uint64_t>(n_sub, 1u << 18));
-          KNN_DISPATCH(knn_bound_kernel, cnt, sorted_xyz.as<double>(), ql, cnt, (const double*)xyz_s.as<double>(), n_bound, k, bound.as<double>());
-          hipLaunchKernelGGL(knn_pack_queries_kernel, dim3((cnt + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, (const double*)sorted_xyz.as<double>(), ql, cnt,
-                             (const double*)bound.as<double>(), qpack.as<double>());
-          hipLaunchKernelGGL(knn_filter_kernel, dim3((unsigned)((nf + kBlock * kFilterPts - 1) / (kBlock * kFilterPts))), dim3(kBlock), 0, stream,
-                             (const double*)sorted_xyz.as<double>(), (uint32_t)nf, (const double*)qpack.as<double>(), cnt, cand_cap, cand_count.as<uint32_t>(),
-                             cand.as<uint32_t>());
-          KNN_DISPATCH(knn_select_kernel, cnt, sorted_xyz.as<double>(), (uint32_t)nf, k, ql, cnt, (const uint32_t*)cand_count.as<uint32_t>(),
-                       (const uint32_t*)cand.as<uint32_t>(), cand_cap, sorted);
-        }
-        mark("all-points");
-        return true;
-#undef ACK
-      };
-      for (int level = 1; nf; ++level) {
-        uint32_t n_open[2] = {0, 0};  // handed back by the shell cap / by the crowd guard
-        NCK(hipMemcpyAsync(n_open, unres_count, 8, hipMemcpyDeviceToHost, stream));
-        NCK(hipStreamSynchronize(stream));
-        NCK(hipMemsetAsync(unres_count, 0, 8, stream));
-        if (n_open[0] || n_open[1]) rec_open = true;
-        if (n_open[1] && !all_points(2, n_open[1])) return -1;
-        const uint32_t n_un = n_open[0];
-        if (!n_un) break;
-        if (level == 1) {  // from here on: the cloud's own axes and its full bounding box
-          frame = GridParams{};
-          for (int c = 0; c < 3; ++c) { mn[c] = full_mn[c]; mx[c] = full_mx[c]; }
-          set_box();
-        }
-        const double h_up = g.h * (double)kShellCap;
-        GridParams trial{};
-        const uint64_t up_cells = grid_for(h_up, 1, trial);
-        const bool last = std::max(trial.dim[0], std::max(trial.dim[1], trial.dim[2])) <= (uint32_t)kShellCap + 1u;
-        const bool up_dense = is_dense(up_cells);
-        // all points or another level?  The all-points search does ~2e12 pairs per second; an index costs ~2 ns per point with a dense
-        // directory and ~4.5 ns with the hash table (64-bit Morton keys, eight radix passes, the table), and may leave queries open.
-        if (search_all_points(level, n_un, nf, up_dense)) {
-          if (!all_points(1, n_un)) return -1;
-          break;
-        }
-        if (debug) fprintf(stderr, "[pst knn] level %d: %u open queries, cell edge %g (%s)%s\n", level, n_un, h_up, up_dense ? "dense" : "hash", last ? ", uncapped" : "");
-        if (!build_index(h_up, 1, up_dense)) return -1;
-        dense = up_dense;
-        NCK(fb_list.alloc((size_t)nf * 4, stream));
-        NCK(hipMemsetAsync(unres_count + 2, 0, 4, stream));
-        hipLaunchKernelGGL(collect_unresolved_kernel, dim3((unsigned)((nf + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, (const uint32_t*)idx2.as<uint32_t>(), (uint32_t)nf,
-                           unres.as<uint8_t>(), (uint8_t)1, fb_list.as<uint32_t>(), unres_count + 2);
-        const unsigned grid = (unsigned)((n_un + kBlock - 1) / kBlock);
-        const int cap = last ? 0 : kShellCap;
-        if (up_dense) {
-          KNN_DISPATCH_GRID(true, true, grid, sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g, table, (const uint32_t*)directory.as<uint32_t>(),
-                            (const uint32_t*)fb_list.as<uint32_t>(), n_un, sorted, cap, unres.as<uint8_t>(), unres_count, kCrowd, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
-        } else {
-          KNN_DISPATCH_GRID(false, true, grid, sorted_xyz.as<double>(), (const uint64_t*)keys2.as<uint64_t>(), (uint32_t)nf, k, g, table, (const uint32_t*)nullptr,
-                            (const uint32_t*)fb_list.as<uint32_t>(), n_un, sorted, cap, unres.as<uint8_t>(), unres_count, kCrowd, open_lists.as<uint32_t>(), kOpenCap, (const uint32_t*)nullptr);
-        }
-        mark("coarser");
-      }
-    }
-    if (nf < n) {
-      // non-finite query points: every distance is NaN (-> +inf), so "the k nearest" is the reference's kd-tree tie order
-      // (unpinned).  Chosen here: the point itself, then the first k-1 finite points in sorted order.
-      const unsigned grid = (unsigned)((n - nf + kBlock - 1) / kBlock);
-      hipLaunchKernelGGL(knn_nonfinite_kernel, dim3(grid), dim3(kBlock), 0, stream, xyz.as<double>(), sorted_xyz.as<double>(), (uint32_t)nf, (uint32_t)n, k,
-                         sorted);
-    }
-    mark("fallback");
-    if (!direct_out) {
-      hipLaunchKernelGGL(split_results_kernel, dim3(sgrid), dim3(kBlock), 0, stream, (const double*)rec.as<double>(), n, out);
-      mark("split");
-    }
-    if (trace) fprintf(stderr, "[pst knn trace]%s\n", trace_line.c_str());
-    NCK(hipGetLastError());
+    if (!call.take_index_arrays() || !call.gate_estimate() || !call.measure_box()) return -1;
+    call.trace.mark("occupancy");
+    if (!call.principal_axes() || !call.measure_scale() || !call.plan_box_search() || !call.global_index() || !call.first_search() || !call.coarser_levels()) return -1;
   }
-  NCK(hipGetLastError());
-  int errors = 0;
-  NCK(hipMemcpyAsync(&errors, out.error_count, 4, hipMemcpyDeviceToHost, stream));
-  NCK(hipStreamSynchronize(stream));
-  if (record && rec_tiled) {
-    if (rec_open) record->why_not = "some queries were handed back by a capped search (far points, sparse regions): the coarser levels are host-driven";
-    else if (rec_nf != n) record->why_not = "the cloud holds non-finite points";
-    else if (!knn_tuning().direct_out) record->why_not = "PST_KNN_DIRECT=0";
-    else if (out_knn_dev) record->why_not = "int64 neighbour lists are a host-side format";
-    else {
-      record->valid = true; record->why_not = "";
-      record->n = n; record->nf = rec_nf; record->cells = rec_cells; record->k = k; record->g = rec_g; record->shape = rec_shape;
-      record->use_list = rec_list; record->n_list = rec_n_list; record->n_fb = rec_n_fb;
-      unsigned kb = 1; while (kb < 32 && (1ull << kb) <= rec_cells) ++kb;
-      record->key_bits = kb;
-    }
-  }
-#undef KNN_DISPATCH_GRID
-#undef KNN_DISPATCH
-#undef KNN_DISPATCH_T
-#undef NCK
-  return errors;
+  return call.finish(record);
 }
 
 
@@ -1671,29 +1752,27 @@ KnnPlan* knn_plan_create(const KnnPlanRecord& rec, bool packed_source, hipStream
   const uint64_t n = rec.n;
   const unsigned cus = (unsigned)device_cus();
   p->sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)cus * 8));
-#define PCK(x) do { if ((x) != hipSuccess) return nullptr; } while (0)
-  if (!packed_source) { PCK(p->xyz_own.alloc(n * 24, stream)); PCK(p->partials.alloc((size_t)p->sgrid * 48, stream)); }
-  PCK(p->counters.alloc(128, stream));
-  PCK(p->keys.alloc(n * 4, stream)); PCK(p->keys2.alloc(n * 4, stream)); PCK(p->idx.alloc(n * 4, stream)); PCK(p->idx2.alloc(n * 4, stream));
-  PCK(p->sorted_xyz.alloc(n * 24, stream));
-  PCK(sort_pairs_u32(nullptr, p->tmp_sort, p->keys.as<uint32_t>(), p->keys2.as<uint32_t>(), p->idx.as<uint32_t>(), p->idx2.as<uint32_t>(), n, rec.key_bits, stream));
-  PCK(p->directory.alloc((rec.cells + 2) * 4, stream));
+  if (!packed_source && (!ok(p->xyz_own.alloc(n * 24, stream)) || !ok(p->partials.alloc((size_t)p->sgrid * 48, stream)))) return nullptr;
+  if (!ok(p->counters.alloc(sizeof(KnnCounters), stream))) return nullptr;
+  if (!ok(p->keys.alloc(n * 4, stream)) || !ok(p->keys2.alloc(n * 4, stream)) || !ok(p->idx.alloc(n * 4, stream)) || !ok(p->idx2.alloc(n * 4, stream))) return nullptr;
+  if (!ok(p->sorted_xyz.alloc(n * 24, stream))) return nullptr;
+  if (!ok(sort_pairs_u32(nullptr, p->tmp_sort, p->keys.as<uint32_t>(), p->keys2.as<uint32_t>(), p->idx.as<uint32_t>(), p->idx2.as<uint32_t>(), n, rec.key_bits, stream))) return nullptr;
+  if (!ok(p->directory.alloc((rec.cells + 2) * 4, stream))) return nullptr;
   if (rec.cells > 3 * rec.nf) {
     p->n_dblocks = (rec.cells + 1 + kDirBlock - 1) / kDirBlock;
-    PCK(p->dir_blocks.alloc(p->n_dblocks * 4, stream));
-    PCK(suffix_min_u32(nullptr, p->tmp_suffix, p->dir_blocks.as<uint32_t>(), p->n_dblocks, stream));
+    if (!ok(p->dir_blocks.alloc(p->n_dblocks * 4, stream))) return nullptr;
+    if (!ok(suffix_min_u32(nullptr, p->tmp_suffix, p->dir_blocks.as<uint32_t>(), p->n_dblocks, stream))) return nullptr;
   }
-  PCK(p->tmp.alloc(std::max(p->tmp_sort, p->tmp_suffix), stream));
-  PCK(p->fb_list.alloc(rec.nf * 4, stream));
+  if (!ok(p->tmp.alloc(std::max(p->tmp_sort, p->tmp_suffix), stream))) return nullptr;
+  if (!ok(p->fb_list.alloc(rec.nf * 4, stream))) return nullptr;
   p->all_boxes = knn_box_count(rec.shape, rec.g);
   if (rec.use_list) {
-    PCK(p->box_list.alloc((size_t)p->all_boxes * 4, stream));
+    if (!ok(p->box_list.alloc((size_t)p->all_boxes * 4, stream))) return nullptr;
     p->list_cap = (uint32_t)std::min<uint64_t>(p->all_boxes, (uint64_t)rec.n_list + rec.n_list / 4 + 1024);  // a quarter more occupied boxes than recorded
   }
   p->fb_cap = (uint32_t)std::min<uint64_t>(rec.nf, (uint64_t)rec.n_fb + rec.n_fb / 2 + 65536);  // half as many more hand-backs than recorded
-  PCK(p->unres.alloc(n, stream));
-  PCK(p->open_lists.alloc((size_t)2 * kReplayOpenCap * 4, stream));
-#undef PCK
+  if (!ok(p->unres.alloc(n, stream))) return nullptr;
+  if (!ok(p->open_lists.alloc((size_t)2 * kReplayOpenCap * 4, stream))) return nullptr;
   return p.release();
 }
 void knn_plan_free(KnnPlan* p) { delete p; }
@@ -1704,13 +1783,13 @@ const KnnPlanRecord& knn_plan_record(const KnnPlan* p) { return p->rec; }
 
 bool run_normals_replay(KnnPlan* p, const uint8_t* pos_base, uint64_t pos_stride, double* out_normals_dev, double* out_curv_dev, uint32_t* out_knn_u32_dev,
                         uint64_t normal_attr, uint64_t normal_stride, uint64_t curv_attr, uint64_t curv_stride, unsigned long long* status2, hipStream_t stream) {
-#define RCK(x) do { if ((x) != hipSuccess) return false; } while (0)
   const KnnPlanRecord& r = p->rec;
   const uint64_t n = r.n, nf = r.nf, cells = r.cells;
   const uint32_t k = r.k;
   const GridParams& g = r.g;
   const unsigned cus = (unsigned)device_cus(), sgrid = p->sgrid;
-  RCK(hipMemsetAsync(p->counters.p, 0, 128, stream));
+  KnnCounters* ctr = p->counters.as<KnnCounters>();
+  if (!ok(hipMemsetAsync(ctr, 0, sizeof(KnnCounters), stream))) return false;
   // packed or not is a property of THIS call's buffer, not of the one the plan was made on (another cloud of the same length may sit in a
   // VectorBuffer): a plan made on a packed column has no staging copy and takes packed sources only (knn_plan_accepts)
   const bool packed_now = pos_stride == 24 && ((uintptr_t)pos_base & 7u) == 0;
@@ -1720,58 +1799,31 @@ bool run_normals_replay(KnnPlan* p, const uint8_t* pos_base, uint64_t pos_stride
     hipLaunchKernelGGL(gather_positions_kernel, dim3(sgrid), dim3(kBlock), 0, stream, pos_base, pos_stride, n, p->xyz_own.as<double>(), p->partials.as<double>());
     src = p->xyz_own.as<double>();
   }
-  unsigned long long* n_finite = (unsigned long long*)p->counters.p;
-  uint32_t* fb_count = (uint32_t*)((uint8_t*)p->counters.p + 16);
-  int* error_count = (int*)((uint8_t*)p->counters.p + 32);
-  uint32_t* unres_count = (uint32_t*)((uint8_t*)p->counters.p + 64);
-  uint32_t* box_count = (uint32_t*)((uint8_t*)p->counters.p + 76);
-  // index: keys (+ the sort's first histogram), sort, permutation, directory -- what build_index does for a dense grid, with the recorded grid
-  {
-    RadixFirstPass walk{nullptr, (uint32_t)((n + 8191) / 8192), 0, 8192};
-    const RadixFirstPass first = sort_first_pass(p->tmp.p, n, r.key_bits);
-    if (first.counts) walk = first;
-    hipLaunchKernelGGL(keys_kernel<uint32_t>, dim3(std::max(1u, std::min(walk.tiles, cus * 16u))), dim3(kBlock), 0, stream, src, n, g, p->keys.as<uint32_t>(), (uint32_t*)nullptr,
-                       n_finite, walk);
-    size_t tb = p->tmp_sort;
-    RCK(sort_pairs_u32(p->tmp.p, tb, p->keys.as<uint32_t>(), p->keys2.as<uint32_t>(), p->idx.as<uint32_t>(), p->idx2.as<uint32_t>(), n, r.key_bits, stream, true, &first));
-    const unsigned rgrid = (unsigned)std::max<uint64_t>(1, (n + (uint64_t)kBlock * 2 - 1) / ((uint64_t)kBlock * 2));
-    hipLaunchKernelGGL(reorder_kernel<2>, dim3(rgrid), dim3(kBlock), 0, stream, src, p->idx2.as<uint32_t>(), n, p->sorted_xyz.as<double>());
-    if (cells > 3 * nf) {
-      RCK(hipMemsetAsync(p->dir_blocks.p, 0xFF, p->n_dblocks * 4, stream));
-      hipLaunchKernelGGL(dir_block_heads_kernel, dim3(sgrid), dim3(kBlock), 0, stream, p->keys2.as<uint32_t>(), nf, cells, p->dir_blocks.as<uint32_t>());
-      size_t sb = p->tmp_suffix;
-      RCK(suffix_min_u32(p->tmp.p, sb, p->dir_blocks.as<uint32_t>(), p->n_dblocks, stream));
-      hipLaunchKernelGGL(dir_fill_kernel, dim3((unsigned)((p->n_dblocks + kDirPerGroup - 1) / kDirPerGroup)), dim3(kBlock), 0, stream, p->keys2.as<uint32_t>(), nf, cells,
-                         (const uint32_t*)p->dir_blocks.as<uint32_t>(), p->n_dblocks, p->directory.as<uint32_t>());
-    } else {
-      hipLaunchKernelGGL(build_directory_kernel, dim3(sgrid), dim3(kBlock), 0, stream, p->keys2.as<uint32_t>(), nf, cells, p->directory.as<uint32_t>());
-    }
-  }
-  const uint32_t* cell_start = p->directory.as<uint32_t>();
+  // index: what build_index does for a dense grid, with the recorded grid and finite count, all on this stream: no read-back, no allocation
+  DenseIndex v{p->keys.as<uint32_t>(), p->keys2.as<uint32_t>(), p->idx.as<uint32_t>(), p->idx2.as<uint32_t>(), p->sorted_xyz.as<double>(), p->tmp.p, p->tmp_sort,
+               p->directory.as<uint32_t>(), p->dir_blocks.as<uint32_t>(), p->n_dblocks};
+  if (!dense_keys_and_sort(v, src, n, g, r.key_bits, &ctr->n_finite, cus, stream)) return false;
+  dense_reorder(v, src, n, 2, stream);
+  v.tmp_bytes = p->tmp_suffix;
+  if (!dense_directory(v, nf, cells, sgrid, stream)) return false;
+  const uint32_t* cell_start = v.directory;
   const uint32_t* list_ptr = nullptr;
   if (r.use_list) {
-    if (!knn_box_list_async(r.shape, cell_start, g, p->box_list.as<uint32_t>(), box_count, stream)) return false;
+    if (!knn_box_list_async(r.shape, cell_start, g, p->box_list.as<uint32_t>(), &ctr->box_count, stream)) return false;
     list_ptr = p->box_list.as<uint32_t>();
   }
-  RCK(hipMemsetAsync(p->unres.p, 0, n, stream));
-  RecOut sorted{nullptr, p->idx2.as<uint32_t>(), nullptr, out_knn_u32_dev, error_count, out_normals_dev, out_curv_dev, normal_attr, normal_stride, curv_attr, curv_stride};
-  launch_knn_tile(r.shape, p->sorted_xyz.as<double>(), cell_start, g, k, (uint32_t)nf, sorted, p->fb_list.as<uint32_t>(), fb_count, list_ptr, p->list_cap, stream,
-                  list_ptr ? box_count : nullptr);
+  if (!ok(hipMemsetAsync(p->unres.p, 0, n, stream))) return false;
+  RecOut sorted{nullptr, p->idx2.as<uint32_t>(), nullptr, out_knn_u32_dev, &ctr->error_count, out_normals_dev, out_curv_dev, normal_attr, normal_stride, curv_attr, curv_stride};
+  launch_knn_tile(r.shape, p->sorted_xyz.as<double>(), cell_start, g, k, (uint32_t)nf, sorted, p->fb_list.as<uint32_t>(), &ctr->fb_count, list_ptr, p->list_cap, stream,
+                  list_ptr ? &ctr->box_count : nullptr);
   // what the box kernel handed back: the exact search over the dense directory, its length read on the device (the list is not sorted by
   // position here: that sort takes its length on the host)
-  {
-    const unsigned grid = (unsigned)((p->fb_cap + kBlock - 1) / kBlock);
-    CellTable table{nullptr, nullptr, 0};
-#define RDISPATCH(K) hipLaunchKernelGGL((knn_grid_kernel<K, true, true>), dim3(grid), dim3(kBlock), 0, stream, (const double*)p->sorted_xyz.as<double>(), (const uint64_t*)nullptr, \
-                                        (uint32_t)nf, k, g, table, cell_start, (const uint32_t*)p->fb_list.as<uint32_t>(), p->fb_cap, sorted, kShellCap, p->unres.as<uint8_t>(), \
-                                        unres_count, 0u, p->open_lists.as<uint32_t>(), kReplayOpenCap, (const uint32_t*)fb_count)
-    if (k <= 8) RDISPATCH(8); else if (k <= 16) RDISPATCH(16); else if (k <= 32) RDISPATCH(32); else RDISPATCH(64);
-#undef RDISPATCH
-  }
-  hipLaunchKernelGGL(knn_replay_status_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)n_finite, (unsigned long long)nf, (const uint32_t*)fb_count, p->fb_cap,
-                     r.use_list ? (const uint32_t*)box_count : (const uint32_t*)nullptr, p->list_cap, (const uint32_t*)unres_count, (const int*)error_count, status2);
+  launch_grid_search<true, true>(k, (unsigned)((p->fb_cap + kBlock - 1) / kBlock), stream, (const double*)p->sorted_xyz.as<double>(), (const uint64_t*)nullptr, (uint32_t)nf, k, g,
+                                 CellTable{nullptr, nullptr, 0}, cell_start, (const uint32_t*)p->fb_list.as<uint32_t>(), p->fb_cap, sorted, kShellCap, p->unres.as<uint8_t>(),
+                                 ctr->open_count, 0u, p->open_lists.as<uint32_t>(), kReplayOpenCap, (const uint32_t*)&ctr->fb_count);
+  hipLaunchKernelGGL(knn_replay_status_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)&ctr->n_finite, (unsigned long long)nf, (const uint32_t*)&ctr->fb_count, p->fb_cap,
+                     r.use_list ? (const uint32_t*)&ctr->box_count : (const uint32_t*)nullptr, p->list_cap, (const uint32_t*)ctr->open_count, (const int*)&ctr->error_count, status2);
   return hipGetLastError() == hipSuccess;
-#undef RCK
 }
 
 }  // namespace pstk

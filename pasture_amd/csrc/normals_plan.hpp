@@ -136,6 +136,38 @@ inline bool take_trimmed_box(int pass, double shrink) { return pass < 3 && shrin
 inline bool consider_rotation(double occupancy, uint64_t n, const KnnTuning& t) { return occupancy < 0.5 && n >= (1u << 16) && !t.no_rotate; }
 inline bool axes_are_coordinate_axes(double align) { return align >= 0.995; }
 inline bool take_rotated_box(double v_rot, double v_now) { return v_rot <= 0.35 * v_now; }
+// The axes themselves, from the ten moment sums {x, y, z, xx, xy, xz, yy, yz, zz, count} of the points about some centre: the eigenvectors of
+// the covariance (cyclic Jacobi) as the rows of an orthonormal matrix, largest variance first -- the grid's rows (x) run along the cloud's
+// longest direction -- and align (1 = the principal axes ARE the coordinate axes, in some order).  The frame feeds the cell keys: the
+// arithmetic is fixed, statement for statement.
+struct PrincipalAxes { double rot[9], align; };
+inline PrincipalAxes principal_axes_of(const double hs[10]) {
+  const double c = hs[9], m0 = hs[0] / c, m1 = hs[1] / c, m2 = hs[2] / c;
+  double A[3][3] = {{hs[3] / c - m0 * m0, hs[4] / c - m0 * m1, hs[5] / c - m0 * m2}, {0, hs[6] / c - m1 * m1, hs[7] / c - m1 * m2}, {0, 0, hs[8] / c - m2 * m2}};
+  A[1][0] = A[0][1]; A[2][0] = A[0][2]; A[2][1] = A[1][2];
+  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};  // columns = eigenvectors
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    const double off = std::fabs(A[0][1]) + std::fabs(A[0][2]) + std::fabs(A[1][2]);
+    if (!(off > 1e-300) || off < 1e-14 * (std::fabs(A[0][0]) + std::fabs(A[1][1]) + std::fabs(A[2][2]))) break;
+    for (int pi = 0; pi < 2; ++pi)
+      for (int qi = pi + 1; qi < 3; ++qi) {
+        if (A[pi][qi] == 0.0) continue;
+        const double theta = (A[qi][qi] - A[pi][pi]) / (2.0 * A[pi][qi]);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0)), cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+        for (int r = 0; r < 3; ++r) { const double arp = A[r][pi], arq = A[r][qi]; A[r][pi] = cs * arp - sn * arq; A[r][qi] = sn * arp + cs * arq; }
+        for (int r = 0; r < 3; ++r) { const double apr = A[pi][r], aqr = A[qi][r]; A[pi][r] = cs * apr - sn * aqr; A[qi][r] = sn * apr + cs * aqr; }
+        for (int r = 0; r < 3; ++r) { const double vrp = V[r][pi], vrq = V[r][qi]; V[r][pi] = cs * vrp - sn * vrq; V[r][qi] = sn * vrp + cs * vrq; }
+      }
+  }
+  int order[3] = {0, 1, 2};
+  std::sort(order, order + 3, [&](int a, int b) { return A[a][a] > A[b][b]; });
+  PrincipalAxes pa{};
+  for (int r = 0; r < 3; ++r)
+    for (int cc = 0; cc < 3; ++cc) pa.rot[3 * r + cc] = V[cc][order[r]];
+  pa.align = 1.0;  // the smallest of the rows' largest components
+  for (int r = 0; r < 3; ++r) pa.align = std::fmin(pa.align, std::fmax(std::fabs(pa.rot[3 * r]), std::fmax(std::fabs(pa.rot[3 * r + 1]), std::fabs(pa.rot[3 * r + 2]))));
+  return pa;
+}
 
 // BOX SEARCH: which clouds try it, with how many fine x cells per h, and whether the directory fits its budget
 inline bool try_box_search(uint32_t k, double occupancy, uint64_t n, const KnnTuning& t) {

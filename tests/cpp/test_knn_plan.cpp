@@ -101,6 +101,53 @@ int main() {
     CHECK(axes_are_coordinate_axes(0.999) && !axes_are_coordinate_axes(0.77));
     CHECK(take_rotated_box(0.1, 1.0) && !take_rotated_box(0.5, 1.0));
   }
+  // the axes themselves (principal_axes_of): moment sums of `count` points about their centre with covariance C, mean zero
+  {
+    auto sums = [](const double (&C)[3][3], double (&hs)[10]) {
+      const double count = 4096.0;
+      hs[0] = hs[1] = hs[2] = 0.0; hs[9] = count;
+      hs[3] = C[0][0] * count; hs[4] = C[0][1] * count; hs[5] = C[0][2] * count; hs[6] = C[1][1] * count; hs[7] = C[1][2] * count; hs[8] = C[2][2] * count;
+    };
+    auto orthonormal_to = [](const PrincipalAxes& pa) {
+      double worst = 0.0;
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+          const double dot = pa.rot[3 * a] * pa.rot[3 * b] + pa.rot[3 * a + 1] * pa.rot[3 * b + 1] + pa.rot[3 * a + 2] * pa.rot[3 * b + 2];
+          worst = std::fmax(worst, std::fabs(dot - (a == b ? 1.0 : 0.0)));
+        }
+      return worst;
+    };
+    double hs[10];
+    // identity covariance: no sweep runs, the axes are the coordinate axes in their own order
+    const double I[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    sums(I, hs);
+    PrincipalAxes pa = principal_axes_of(hs);
+    for (int i = 0; i < 9; ++i) CHECK(pa.rot[i] == (i % 4 == 0 ? 1.0 : 0.0));
+    CHECK(pa.align == 1.0);
+    // a diagonal covariance in permuted order (variances 1, 9, 4): rows by descending variance = y, z, x
+    const double Dg[3][3] = {{1, 0, 0}, {0, 9, 0}, {0, 0, 4}};
+    sums(Dg, hs);
+    pa = principal_axes_of(hs);
+    const double want[9] = {0, 1, 0, 0, 0, 1, 1, 0, 0};
+    for (int i = 0; i < 9; ++i) CHECK(pa.rot[i] == want[i]);
+    CHECK(pa.align == 1.0);
+    // a slab (variances 100, 4, 1 along its own axes) tilted by 30 degrees about z: C = R diag R^T
+    const double c30 = std::cos(M_PI / 6), s30 = std::sin(M_PI / 6);
+    const double S[3][3] = {{100 * c30 * c30 + 4 * s30 * s30, (100 - 4) * c30 * s30, 0}, {(100 - 4) * c30 * s30, 100 * s30 * s30 + 4 * c30 * c30, 0}, {0, 0, 1}};
+    sums(S, hs);
+    pa = principal_axes_of(hs);
+    const double sign = pa.rot[0] < 0 ? -1.0 : 1.0;  // (an eigenvector's sign is free)
+    CHECK(std::fabs(sign * pa.rot[0] - c30) <= 1e-12 && std::fabs(sign * pa.rot[1] - s30) <= 1e-12 && std::fabs(pa.rot[2]) <= 1e-12);
+    CHECK(orthonormal_to(pa) <= 1e-14);
+    CHECK(!axes_are_coordinate_axes(pa.align) && std::fabs(pa.align - c30) <= 1e-12);
+    // a rank-1 covariance (all points on the line along (1, 2, 3)): the sweeps end, every value is finite
+    const double L[3][3] = {{1, 2, 3}, {2, 4, 6}, {3, 6, 9}};
+    sums(L, hs);
+    pa = principal_axes_of(hs);
+    for (int i = 0; i < 9; ++i) CHECK(std::isfinite(pa.rot[i]));
+    CHECK(std::isfinite(pa.align) && orthonormal_to(pa) <= 1e-14);
+    CHECK(std::fabs(std::fabs(pa.rot[0] * 1 + pa.rot[1] * 2 + pa.rot[2] * 3) - std::sqrt(14.0)) <= 1e-12);  // the first row is the line
+  }
   // global-memory search: cell edges from the measured scale of a surface (dimension 2): a cell holds k / 12 * 3 points
   {
     const double mn[3] = {0, 0, 0}, mx[3] = {500, 500, 40};

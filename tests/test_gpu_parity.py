@@ -1158,6 +1158,108 @@ def test_box_search_forced_on_sparse_clouds_vs_oracle(hip, oracle, monkeypatch, 
     assert bad.sum() == 0 and cbad.sum() == 0
 
 
+def _host_path_cloud(name):
+    """Continuous coordinates throughout: the k-th and (k+1)-th neighbour distances of every query differ, so the lists are unique."""
+    if name == "volume":
+        return _normals_inputs(20_000, 5, "volume")
+    if name == "surface":
+        return _normals_inputs(60_000, 5, "surface")
+    rng = np.random.default_rng(17)
+    if name == "tilted_slab":  # 1000 x 40 x 10, turned by 30 degrees about z: thin along a direction that is no coordinate axis (>= 2^16 points)
+        p = rng.random((70_000, 3)) * np.array([1000.0, 40.0, 10.0])
+        c, s = np.cos(np.pi / 6), np.sin(np.pi / 6)
+        return np.column_stack([c * p[:, 0] - s * p[:, 1], s * p[:, 0] + c * p[:, 1], p[:, 2]])
+    if name == "volume_with_strays":  # eight points a thousand extents away stretch the bounding box
+        strays = (rng.random((8, 3)) * 2.0 - 1.0) * np.array([1000.0, 1000.0, 100.0]) * 1e3
+        return np.concatenate([_normals_inputs(20_000, 5, "volume"), strays])
+    if name == "volume_with_nans":
+        pts = _normals_inputs(5_000, 5, "volume")
+        pts[[3, 2_500, 4_999]] = np.array([[np.nan, 1.0, 2.0], [np.nan, np.nan, np.nan], [5.0, 6.0, np.nan]])
+        return pts
+    raise ValueError(name)
+
+
+_HOST_PATH_ORACLE = {}  # cloud name -> the oracle's (normals, curvature, lists): computed once, shared by the cases of that cloud, never modified
+
+_HOST_PATHS = [
+    ("dense global search", "volume", {"PST_KNN_NO_TILE": "1"}),
+    ("hash table", "volume", {"PST_KNN_NO_TILE": "1", "PST_KNN_DENSE": "0"}),
+    ("records + split", "volume", {"PST_KNN_DIRECT": "0"}),
+    ("reorder on the caller's stream, unroll 1", "volume", {"PST_KNN_SIDE_STREAM": "0", "PST_REORDER_UNROLL": "1"}),
+    ("reorder on the caller's stream, unroll 4", "volume", {"PST_KNN_SIDE_STREAM": "0", "PST_REORDER_UNROLL": "4"}),
+    ("every box launched", "surface", {"PST_KNN_FORCE_TILE": "1", "PST_KNN_BOX_LIST": "0"}),
+    ("rotated frame", "tilted_slab", {}),
+    ("rotated frame off", "tilted_slab", {"PST_KNN_NO_ROTATE": "1"}),
+    ("trimmed box", "volume_with_strays", {}),
+    ("trimmed box off", "volume_with_strays", {"PST_KNN_NO_TRIM": "1"}),
+    ("non-finite points", "volume_with_nans", {}),
+]
+
+
+@pytest.mark.parametrize("what,cloud,switches", _HOST_PATHS, ids=[c[0] for c in _HOST_PATHS])
+def test_knn_host_paths_behind_switches_vs_oracle(hip, oracle, monkeypatch, what, cloud, switches):
+    """The paths of the kNN host driver that only a tuning switch (or a rare cloud) reaches: the global-memory search over the dense
+    directory and over the hash table, 32-byte records + the split pass, the reorder on the caller's stream with every unroll, one workgroup
+    for every box, the rotated frame and the trimmed box on and off, non-finite points.  Lists equal to the oracle's, normals within 1e-9.
+    Non-finite points: every distance to or from them is NaN.  The reference's kd-tree has no order for them (built over such a cloud it
+    loses neighbours of FINITE queries too: 4712 of 4997 lists differ from a brute-force search), so the oracle runs on the finite points
+    alone -- no finite query's list can hold a non-finite point -- and its lists are mapped back to the cloud's numbering; the non-finite
+    rows are held to this library's rule -- the point itself, then finite points, no point twice -- and to the oracle's fit of those lists."""
+    from pasture_amd.algorithms import compute_normals, reload_tuning
+    pts = _host_path_cloud(cloud)
+    n, k = len(pts), 16
+    finite = np.isfinite(pts).all(axis=1)
+
+    def run(api, p=pts):
+        buf = HashMapBuffer.new_from_layout(PointLayout.from_attributes([A.POSITION_3D], api=api))
+        buf.resize(len(p))
+        buf.set_attribute_range(A.POSITION_3D, range(0, len(p)), p)
+        return compute_normals(buf, k, return_knn=True)
+    if cloud not in _HOST_PATH_ORACLE:
+        if finite.all():
+            _HOST_PATH_ORACLE[cloud] = run(oracle)
+        else:
+            sub = np.flatnonzero(finite)
+            sn, sc, sk = run(oracle, pts[sub])
+            on, oc, ok = np.zeros((n, 3)), np.zeros(n), np.zeros((n, k), dtype=np.int64)
+            on[sub], oc[sub], ok[sub] = sn, sc, sub[sk]
+            _HOST_PATH_ORACLE[cloud] = (on, oc, ok)
+    on, oc, ok = _HOST_PATH_ORACLE[cloud]
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    reload_tuning(hip)  # the switches are read once per process
+    try:
+        hn, hc, hk = run(hip)
+    finally:
+        monkeypatch.undo()
+        reload_tuning(hip)
+    assert np.array_equal(hk[finite], ok[finite]), what
+    bad, cbad = _compare_normals(hn[finite], hc[finite], on[finite], oc[finite], scales=_cov_scales(pts, ok)[finite])
+    assert bad.sum() == 0 and cbad.sum() == 0, what
+    if not finite.all():
+        q = np.flatnonzero(~finite)
+        assert np.array_equal(hk[q, 0], q) and finite[hk[q, 1:]].all() and all(len(set(row)) == k for row in hk[q].tolist())
+        bad, cbad = _compare_normals(hn[q], hc[q], *_oracle_fit_of_lists(oracle, pts, hk[q]))
+        assert bad.sum() == 0 and cbad.sum() == 0, what
+
+
+def test_compute_normals_into_from_a_staged_source_equals_the_packed_call(hip):
+    """A position column that is no packed Vec3f64 array (a VectorBuffer with one more attribute: stride 26) is staged into one first; the
+    NORMAL and Curvature columns are, byte for byte, those of the same points in a HashMapBuffer, which is searched in place."""
+    from pasture_amd.algorithms import compute_normals_into
+    pts = _host_path_cloud("volume")
+    n, k = len(pts), 16
+    curv = PointAttributeDefinition("Curvature", T.F64)
+    staged = VectorBuffer.new_from_layout(PointLayout.from_attributes_packed([A.INTENSITY, A.POSITION_3D], 1, api=hip))
+    staged.resize(n)
+    staged.set_attribute_range(A.POSITION_3D, range(0, n), pts)
+    got, want = _normal_targets(hip, n), _normal_targets(hip, n)
+    compute_normals_into(staged, k, got)
+    compute_normals_into(_cloud_buffer(hip, pts), k, want)
+    assert got.view_attribute(A.NORMAL).tobytes() == want.view_attribute(A.NORMAL).tobytes()
+    assert got.view_attribute(curv).tobytes() == want.view_attribute(curv).tobytes()
+
+
 @pytest.mark.parametrize("var", ["1", "B", "D", "G"])
 @pytest.mark.parametrize("shape,n,k", [("volume", 200_000, 16), ("surface", 1_200_000, 16), ("volume", 150_000, 7)])
 def test_every_instance_of_the_box_kernel_vs_oracle(hip, oracle, monkeypatch, var, shape, n, k):
