@@ -426,6 +426,41 @@ int pst_line_inlier_mask_device(const pst_buffer* b, const double line[6], doubl
  * workgroup, workgroups per compute unit of one grid pass, hypotheses scored per pass over the positions.  Host only. */
 int pst_ransac_kernel_shape(uint32_t* points_per_wave, uint32_t* points_per_block, uint32_t* blocks_per_cu, uint32_t* batch);
 
+/* ---- kNN search and outlier removal -------------------------------------------------------------------------------------------------
+ * The neighbour search of compute_normals as an entry point of its own, with the neighbour DISTANCES, and the two outlier criteria every
+ * LiDAR pipeline runs between "read" and "normals" (the definitions of PCL's / PDAL's StatisticalOutlierRemoval and RadiusOutlierRemoval;
+ * the reference has neither).  The masks are one byte per point, 1 = keep: what pst_buffer_filter / pst_buffer_filter_into take.
+ * Checks and limits of pst_compute_normals_device: fewer than 3 points -> PST_ERR_TOO_FEW_POINTS, k < 3 -> PST_ERR_K_TOO_SMALL, Position3D
+ * not stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE, k > 64 or 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED; interleaved or columnar,
+ * owned, sliced or external.  Degenerate plane fits are NOT an error here (no plane is asked for).  Null arguments and invalid parameters are
+ * answered before a device is looked for, the cloud's length after it; without a device every call is PST_ERR_NO_DEVICE, never a CPU path.
+ * All three calls are synchronous (the search is host-driven).
+ *   distance of slot t of query q, neighbour p:  dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;  d = sqrt((dx*dx + dy*dy) + dz*dz),
+ * every operation a separately rounded f64 operation.  A padded slot (index 0xFFFFFFFF: clouds of fewer than k points) has distance +inf;
+ * non-finite coordinates give what IEEE arithmetic gives. */
+/* d_knn (device, nullable): uint32 [n][k], exactly what pst_compute_normals_device writes.  d_dist (device, required): f64 [n][k]. */
+int pst_knn_search_device(const pst_buffer* b, size_t k, uint32_t* d_knn, double* d_dist);
+/* Statistical outlier removal.  Per point dbar = (d[1] + d[2] + ... + d[mean_k]) / (double)mean_k over its list in ascending distance, summed
+ * left to right; slot 0 (the query or a coincident point, distance 0 either way) is skipped, so dbar depends on the sorted multiset of
+ * distances only.  The search runs with k = max(mean_k + 1, 3).  Over the m points whose dbar is finite: mean = sum(dbar) / m,
+ * stddev = sqrt(sum((dbar - mean)^2) / (m - 1)) in a second pass (0 when m < 2), threshold = mean + stddev_mult * stddev;
+ * stats = {mean, stddev, threshold, (double)m}.  mask[i] = 1 iff dbar_i is finite and dbar_i <= threshold; *kept = their number.  Both sums
+ * are fixed-shape reductions (blocks of a fixed number of points, a fixed tree per block, the block partials added in block order by one
+ * workgroup, no floating-point atomics): two calls on one cloud give the same bits.  mask: len bytes in device memory (mask_memkind =
+ * PST_MEM_DEVICE) or host memory (anything else), the convention of pst_buffer_filter_into.  d_mean_dist (device, nullable): f64 [n], dbar.
+ * mean_k outside 1 .. 63 or a NaN stddev_mult -> PST_ERR_INVALID_ARGUMENT; fewer than mean_k + 1 points -> PST_ERR_TOO_FEW_POINTS. */
+int pst_statistical_outlier_mask(const pst_buffer* b, size_t mean_k, double stddev_mult, uint8_t* mask, uint32_t mask_memkind, double* d_mean_dist, double stats[4],
+                                 uint64_t* kept);
+/* Radius outlier removal.  mask[i] = 1 iff at least min_neighbours points other than point i itself lie within `radius` of it, that is iff
+ * d[i][min_neighbours] <= radius; a padded slot or a NaN distance compares false, so a cloud of min_neighbours points or fewer keeps nothing.
+ * The search runs with k = max(min_neighbours + 1, 3).  min_neighbours outside 1 .. 63, a negative or non-finite radius ->
+ * PST_ERR_INVALID_ARGUMENT. */
+int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neighbours, uint8_t* mask, uint32_t mask_memkind, uint64_t* kept);
+/* The kernels' seams (tests place their sizes around them; each pointer optional): points whose whole neighbour lists one workgroup of the
+ * distance kernels owns (whatever k), threads of the one workgroup that adds the block partials of the sums (each a contiguous run of them),
+ * points per block partial.  Host only. */
+int pst_outlier_kernel_shape(uint32_t* points_per_block, uint32_t* reduce_block, uint32_t* reduce_points_per_block);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -11,6 +11,7 @@ from .buffers import ExternalColumnsBuffer, ExternalMemoryBuffer, HashMapBuffer,
 from .conversion import BufferLayoutConverter, RawPointConverter, Transform  # noqa: F401
 from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute_centroid, compute_normals, compute_normals_into, minmax_attribute, voxelgrid_filter,  # noqa: F401
                          transform_attribute, Line, Plane, line_inlier_mask, line_inliers, plane_inlier_mask, plane_inliers, ransac_line,
-                         ransac_line_fit, ransac_plane, ransac_plane_fit, ransac_sample_indices)
+                         ransac_line_fit, ransac_plane, ransac_plane_fit, ransac_sample_indices, OutlierStatistics, knn_search, knn_search_device,
+                         outlier_kernel_shape, radius_outlier_mask, remove_radius_outliers, remove_statistical_outliers, statistical_outlier_mask)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

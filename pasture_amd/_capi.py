@@ -190,6 +190,10 @@ _PRODUCT_SIGNATURES = {
     "plane_inlier_mask_device": [_P, _D3, C.c_double, _P],
     "line_inlier_mask_device": [_P, _D3, C.c_double, _P],
     "ransac_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
+    "knn_search_device": [_P, _SZ, _P, _P],
+    "statistical_outlier_mask": [_P, _SZ, C.c_double, _P, C.c_uint32, _P, _D3, _U64P],
+    "radius_outlier_mask": [_P, C.c_double, _SZ, _P, C.c_uint32, _U64P],
+    "outlier_kernel_shape": [_U32P, _U32P, _U32P],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -326,3 +326,102 @@ def ransac_kernel_shape(api=None) -> dict:
     v = [C.c_uint32() for _ in range(4)]
     (api or product_api()).ransac_kernel_shape(*[C.byref(x) for x in v])
     return dict(zip(("points_per_wave", "points_per_block", "blocks_per_cu", "batch"), (x.value for x in v)))
+
+
+# ---- kNN search with distances, statistical and radius outlier removal (include/pasture_amd.h) ---------------------------------------------
+
+class _DeviceArray:
+    """`count` values of one scalar datatype in device memory the library owns: a one-attribute columnar buffer (no torch needed)."""
+
+    def __init__(self, api, datatype, count: int):
+        from .buffers import HashMapBuffer
+        from .layout import PointLayout
+        self.attribute = PointAttributeDefinition.custom("Values", datatype)
+        self.buffer = HashMapBuffer.new_from_layout(PointLayout.from_attributes([self.attribute], api=api))
+        self.buffer.resize(count)
+        self.ptr = self.buffer.column_ptr(self.attribute)
+
+    def to_numpy(self) -> np.ndarray:
+        return self.buffer.view_attribute(self.attribute)
+
+
+def knn_search_device(point_cloud: _Buffer, k: int, distances_ptr: int, knn_ptr: int = 0) -> None:
+    """The neighbour lists of compute_normals with their distances, in caller-owned DEVICE memory: distances f64 [n][k] (required), indices
+    uint32 [n][k] (0 = not wanted), both in ascending distance; a padded slot is 0xFFFFFFFF at distance +inf."""
+    point_cloud.api.knn_search_device(point_cloud._h, k, C.c_void_p(knn_ptr or None), C.c_void_p(distances_ptr or None))
+
+
+def knn_search(point_cloud: _Buffer, k: int):
+    """(indices (n, k) int64 with -1 padding, distances (n, k) float64): the k nearest neighbours of every point, itself included, ascending."""
+    from .layout import PointAttributeDataType as T
+    n = point_cloud.len()
+    count = n * max(k, 0) if 3 <= k <= 64 and n >= 3 else 0  # (anything else is answered by the call's own checks)
+    knn, dist = _DeviceArray(point_cloud.api, T.U32, count), _DeviceArray(point_cloud.api, T.F64, count)
+    point_cloud.api.knn_search_device(point_cloud._h, k, C.c_void_p(knn.ptr or None), C.c_void_p(dist.ptr or 1))
+    idx = knn.to_numpy().astype(np.int64).reshape(n, k)
+    idx[idx == 0xFFFFFFFF] = -1
+    return idx, dist.to_numpy().reshape(n, k)
+
+
+@dataclass(frozen=True)
+class OutlierStatistics:
+    """What the statistical criterion measured: over the `count` points with a finite mean neighbour distance, its mean and (sample) standard
+    deviation; threshold = mean + stddev_mult * stddev; kept = points with a finite mean distance <= threshold."""
+    mean: float
+    stddev: float
+    threshold: float
+    count: int
+    kept: int
+
+
+def statistical_outlier_mask(buffer: _Buffer, mean_k: int, stddev_mult: float, device_mask_ptr: Optional[int] = None, return_mean_distances: bool = False):
+    """PCL's / PDAL's statistical outlier criterion on the device: per point the mean distance to its mean_k nearest neighbours; keep those
+    within mean + stddev_mult * stddev of all points' means.  Returns (mask, OutlierStatistics[, mean distances (n,) float64]); mask is a
+    numpy uint8 array (1 = keep), or None when the bytes went to DEVICE memory at device_mask_ptr -- what filter takes as (ptr, 'device')."""
+    from .layout import PointAttributeDataType as T
+    n = buffer.len()
+    stats, kept = (C.c_double * 4)(), C.c_uint64()
+    mask = np.zeros(n, dtype=np.uint8) if device_mask_ptr is None else None
+    dbar = _DeviceArray(buffer.api, T.F64, n if 1 <= mean_k <= 63 and n >= max(3, mean_k + 1) else 0) if return_mean_distances else None
+    ptr = C.c_void_p(int(device_mask_ptr) or None) if mask is None else C.c_void_p(mask.ctypes.data if n else 1)
+    buffer.api.statistical_outlier_mask(buffer._h, mean_k, stddev_mult, ptr, 0 if mask is None else 1, C.c_void_p(dbar.ptr or None) if dbar else None, stats,
+                                        C.byref(kept))
+    st = OutlierStatistics(stats[0], stats[1], stats[2], int(stats[3]), kept.value)
+    return (mask, st, dbar.to_numpy()) if return_mean_distances else (mask, st)
+
+
+def radius_outlier_mask(buffer: _Buffer, radius: float, min_neighbours: int, device_mask_ptr: Optional[int] = None):
+    """Keep the points with at least min_neighbours other points within `radius`.  Returns (mask, kept); mask as in statistical_outlier_mask."""
+    n = buffer.len()
+    kept = C.c_uint64()
+    mask = np.zeros(n, dtype=np.uint8) if device_mask_ptr is None else None
+    ptr = C.c_void_p(int(device_mask_ptr) or None) if mask is None else C.c_void_p(mask.ctypes.data if n else 1)
+    buffer.api.radius_outlier_mask(buffer._h, radius, min_neighbours, ptr, 0 if mask is None else 1, C.byref(kept))
+    return mask, kept.value
+
+
+def _filter_by_device_mask(buffer: _Buffer, out_buffer_type, fill):
+    from .layout import PointAttributeDataType as T
+    mask = _DeviceArray(buffer.api, T.U8, buffer.len())
+    result = fill(mask.ptr)
+    return buffer.filter(out_buffer_type or type(buffer), (mask.ptr, "device")), result
+
+
+def remove_statistical_outliers(buffer: _Buffer, mean_k: int, stddev_mult: float, out_buffer_type=None):
+    """(the points statistical_outlier_mask keeps, OutlierStatistics): mask and compaction stay in device memory.  `buffer` is columnar
+    (filter is defined on HashMapBuffer)."""
+    return _filter_by_device_mask(buffer, out_buffer_type, lambda p: statistical_outlier_mask(buffer, mean_k, stddev_mult, device_mask_ptr=p)[1])
+
+
+def remove_radius_outliers(buffer: _Buffer, radius: float, min_neighbours: int, out_buffer_type=None):
+    """(the points radius_outlier_mask keeps, their number)."""
+    return _filter_by_device_mask(buffer, out_buffer_type, lambda p: radius_outlier_mask(buffer, radius, min_neighbours, device_mask_ptr=p)[1])
+
+
+def outlier_kernel_shape(api=None) -> dict:
+    """The seams of the outlier kernels: points per workgroup of the distance kernels, threads of the workgroup that adds the block partials of
+    the sums, points per block partial."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).outlier_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "reduce_block", "reduce_points_per_block"), (x.value for x in v)))

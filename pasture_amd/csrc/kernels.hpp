@@ -193,4 +193,21 @@ bool ransac_mask(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64
 bool ransac_index_pass(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const void* rec, uint32_t* counts, const unsigned long long* offsets,
                        unsigned long long* indices, bool write, hipStream_t stream);
 
+// Neighbour distances and outlier masks over the kNN lists (outliers.hip).  The kernels' seams (pst_outlier_kernel_shape):
+constexpr uint32_t kOutlierPointsPerBlock = 64;   // a workgroup of the distance kernels owns the whole lists of this many points, whatever k
+constexpr uint32_t kOutlierReduceBlock = 256;     // threads of the one workgroup that adds the block partials, each a contiguous run of them
+constexpr uint32_t kOutlierReducePoints = 1024;   // points per block partial of the sums
+size_t outlier_record_bytes();                    // the result record: {mean, stddev, threshold, (double)m} as doubles, then the kept count (u64)
+size_t outlier_partials_bytes(uint64_t n);
+// knn_dev: uint32 [n][k] as run_normals writes them.  dist_dev: f64 [n][k]
+bool outlier_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, const uint32_t* knn_dev, double* dist_dev, hipStream_t stream);
+// dbar_dev[q] = (d[q][1] + ... + d[q][mean_k]) / mean_k, mean_k < k
+bool outlier_mean_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t mean_k, const uint32_t* knn_dev, double* dbar_dev,
+                            hipStream_t stream);
+// count and sum -> mean -> squared deviations -> stddev, threshold -> mask and kept count; partials: outlier_partials_bytes(n), record: outlier_record_bytes()
+bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stddev_mult, void* partials, void* record, uint8_t* mask_dev, hipStream_t stream);
+// mask[q] = d[q][slot] <= radius; the record's kept count
+bool outlier_radius_mask(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record,
+                         uint8_t* mask_dev, hipStream_t stream);
+
 }  // namespace pstk

@@ -1,0 +1,159 @@
+// pst_knn_search_device / pst_statistical_outlier_mask / pst_radius_outlier_mask: argument checks and plumbing between the kNN search
+// (pstk::run_normals with only the uint32 neighbour lists requested, as pst_compute_normals_device calls it) and outliers.hip.
+#include <cmath>
+
+#include "device_sort.hpp"
+#include "runtime.hpp"
+
+using namespace pst;
+
+namespace {
+
+struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };
+
+// The checks of pst_compute_normals_device in two halves: what the arguments and the layout alone decide is answered before a device is looked
+// for, the cloud's length after it (so a call without a device is PST_ERR_NO_DEVICE whatever the buffer holds).
+const Member& checked_arguments(const pst_buffer& b, size_t k, const char* who) {
+  if (k < 3) throw Error(PST_ERR_K_TOO_SMALL, "The k nearest neigbors attribute is too small!");
+  if (k > 64) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": k > 64 is not supported by the register-resident k-best list");
+  const Member* m = position_vec3f64(b);
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  return *m;
+}
+void checked_length(const pst_buffer& b, size_t at_least, const char* who) {
+  if (b.len < 3) throw Error(PST_ERR_TOO_FEW_POINTS, "The point cloud is too small. Please use a point cloud that has 3 or more points!");
+  if (b.len < at_least) throw Error(PST_ERR_TOO_FEW_POINTS, std::string(who) + ": the point cloud needs at least " + std::to_string(at_least) + " points");
+  if (b.len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+}
+
+PosView position_view(const pst_buffer& b, const Member& m) {
+  const AttrView v = attr_view(b, &m);
+  return PosView{(const uint8_t*)(uintptr_t)v.addr, v.stride, b.len};
+}
+
+// the neighbour lists only; degenerate plane fits (a positive return) are no error here: the lists are written whatever the fit says
+void search(const PosView& pv, size_t k, uint32_t* d_knn, hipStream_t s, const char* who) {
+  const long long rc = pstk::run_normals(pv.base, pv.stride, pv.n, (uint32_t)k, nullptr, nullptr, nullptr, d_knn, 0, 0, 0, 0, s);
+  if (rc == -2) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+  if (rc < 0) throw hip_failure(std::string(who) + ": neighbour search failed: ");
+}
+
+struct Scratch {
+  pstk::DevBuf buf;
+  uint8_t* get(size_t bytes, hipStream_t s, const char* who) {
+    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure(std::string(who) + ": scratch allocation failed: ");
+    return (uint8_t*)buf.p;
+  }
+};
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+void check_mask_args(const uint8_t* mask, uint32_t mask_memkind, const uint64_t* kept) {
+  not_null(mask, "mask");
+  not_null(kept, "kept");
+  if (mask_memkind > PST_MEM_PINNED_HOST) throw Error(PST_ERR_INVALID_ARGUMENT, "invalid mask memory kind");
+}
+
+struct HostRecord { double stats[4]; unsigned long long kept; };
+
+}  // namespace
+
+extern "C" {
+
+int pst_outlier_kernel_shape(uint32_t* points_per_block, uint32_t* reduce_block, uint32_t* reduce_points_per_block) {
+  if (points_per_block) *points_per_block = pstk::kOutlierPointsPerBlock;
+  if (reduce_block) *reduce_block = pstk::kOutlierReduceBlock;
+  if (reduce_points_per_block) *reduce_points_per_block = pstk::kOutlierReducePoints;
+  return PST_OK;
+}
+
+int pst_knn_search_device(const pst_buffer* b, size_t k, uint32_t* d_knn, double* d_dist) {
+  PST_API_BEGIN
+  const char* who = "pst_knn_search_device";
+  not_null(b, "buffer");
+  not_null(d_dist, "d_dist");
+  const Member& pm = checked_arguments(*b, k, who);
+  ensure_device();
+  checked_length(*b, 3, who);
+  hipStream_t s = current_stream();
+  const PosView pv = position_view(*b, pm);
+  Scratch own;
+  if (!d_knn) d_knn = (uint32_t*)own.get(pv.n * k * sizeof(uint32_t), s, who);
+  search(pv, k, d_knn, s, who);
+  if (!pstk::outlier_distances(pv.base, pv.stride, pv.n, (uint32_t)k, d_knn, d_dist, s)) throw hip_failure("knn_search: distance launch failed: ");
+  stream_sync(s);
+  PST_API_END
+}
+
+int pst_statistical_outlier_mask(const pst_buffer* b, size_t mean_k, double stddev_mult, uint8_t* mask, uint32_t mask_memkind, double* d_mean_dist, double stats[4],
+                                 uint64_t* kept) {
+  PST_API_BEGIN
+  const char* who = "pst_statistical_outlier_mask";
+  not_null(b, "buffer");
+  check_mask_args(mask, mask_memkind, kept);
+  not_null(stats, "stats");
+  if (mean_k < 1 || mean_k > 63) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": mean_k must be between 1 and 63");
+  if (std::isnan(stddev_mult)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": stddev_mult is NaN");
+  const size_t k = std::max<size_t>(mean_k + 1, 3);
+  const Member& pm = checked_arguments(*b, k, who);
+  ensure_device();
+  checked_length(*b, mean_k + 1, who);
+  hipStream_t s = current_stream();
+  const PosView pv = position_view(*b, pm);
+  const size_t n = pv.n;
+  const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
+  // one block of scratch: neighbour lists | dbar (unless the caller takes it) | block partials | result record | mask (host masks)
+  const size_t off_dbar = up256(n * k * sizeof(uint32_t));
+  const size_t off_part = off_dbar + (d_mean_dist ? 0 : up256(n * sizeof(double)));
+  const size_t off_rec = off_part + up256(pstk::outlier_partials_bytes(n));
+  const size_t off_mask = off_rec + up256(pstk::outlier_record_bytes());
+  Scratch scratch;
+  uint8_t* base = scratch.get(off_mask + (mask_on_device ? 0 : n), s, who);
+  uint32_t* d_knn = (uint32_t*)base;
+  double* dbar = d_mean_dist ? d_mean_dist : (double*)(base + off_dbar);
+  uint8_t* mask_dev = mask_on_device ? mask : base + off_mask;
+  search(pv, k, d_knn, s, who);
+  if (!pstk::outlier_mean_distances(pv.base, pv.stride, n, (uint32_t)k, (uint32_t)mean_k, d_knn, dbar, s) ||
+      !pstk::outlier_statistics_and_mask(dbar, n, stddev_mult, base + off_part, base + off_rec, mask_dev, s))
+    throw hip_failure("statistical outlier launch failed: ");
+  HostRecord r{};
+  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_rec, sizeof(r), hipMemcpyDeviceToHost, s));
+  if (!mask_on_device) PST_HIP_CHECK(hipMemcpyAsync(mask, mask_dev, n, hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  for (int i = 0; i < 4; ++i) stats[i] = r.stats[i];
+  *kept = r.kept;
+  PST_API_END
+}
+
+int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neighbours, uint8_t* mask, uint32_t mask_memkind, uint64_t* kept) {
+  PST_API_BEGIN
+  const char* who = "pst_radius_outlier_mask";
+  not_null(b, "buffer");
+  check_mask_args(mask, mask_memkind, kept);
+  if (min_neighbours < 1 || min_neighbours > 63) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": min_neighbours must be between 1 and 63");
+  if (!(radius >= 0.0) || std::isinf(radius)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": radius must be finite and not negative");
+  const size_t k = std::max<size_t>(min_neighbours + 1, 3);
+  const Member& pm = checked_arguments(*b, k, who);
+  ensure_device();
+  checked_length(*b, 3, who);
+  hipStream_t s = current_stream();
+  const PosView pv = position_view(*b, pm);
+  const size_t n = pv.n;
+  const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
+  const size_t off_rec = up256(n * k * sizeof(uint32_t));
+  const size_t off_mask = off_rec + up256(pstk::outlier_record_bytes());
+  Scratch scratch;
+  uint8_t* base = scratch.get(off_mask + (mask_on_device ? 0 : n), s, who);
+  uint32_t* d_knn = (uint32_t*)base;
+  uint8_t* mask_dev = mask_on_device ? mask : base + off_mask;
+  search(pv, k, d_knn, s, who);
+  if (!pstk::outlier_radius_mask(pv.base, pv.stride, n, (uint32_t)k, (uint32_t)min_neighbours, radius, d_knn, base + off_rec, mask_dev, s))
+    throw hip_failure("radius outlier launch failed: ");
+  HostRecord r{};
+  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_rec, sizeof(r), hipMemcpyDeviceToHost, s));
+  if (!mask_on_device) PST_HIP_CHECK(hipMemcpyAsync(mask, mask_dev, n, hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  *kept = r.kept;
+  PST_API_END
+}
+
+}  // extern "C"
