@@ -461,6 +461,45 @@ int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neigh
  * points per block partial.  Host only. */
 int pst_outlier_kernel_shape(uint32_t* points_per_block, uint32_t* reduce_block, uint32_t* reduce_points_per_block);
 
+/* ---- Euclidean cluster extraction (radius connected components) ----------------------------------------------------------------------
+ * What PCL's EuclideanClusterExtraction / PDAL's filters.cluster compute (the reference has neither): the points are split into connected
+ * groups, "two points belong together when they are closer than a tolerance", and the groups come back largest first.  The definition:
+ *   finite point:  all three coordinates of its Position3D (Vec3f64) are finite; a point with a NaN or +-inf coordinate is in no cluster.
+ *   adjacency:     finite points i and j are adjacent iff (dx*dx + dy*dy) + dz*dz <= t2, dx = pj.x - pi.x (y, z alike), every operation a
+ *                  separately rounded f64 operation, t2 = tolerance * tolerance rounded once on the host.  There is no sqrt: this differs
+ *                  from sqrt(d2) <= tolerance only where d2 and t2 lie within an ulp or two of each other (sqrt rounds once more, and a d2
+ *                  just above t2 can round down onto the tolerance).
+ *   cluster:       a connected component of that graph -- it depends on nothing else: not on the grid, the traversal order or the schedule.
+ *   size filter:   clusters of fewer than min_size or more than max_size points are dropped; their points are in no cluster.
+ *   numbering:     the kept clusters are numbered 0, 1, ... by descending size, ties by ascending smallest member index (index in the
+ *                  buffer): cluster 0 is the largest.
+ *   labels:        labels[i] = the cluster number of point i, or 0xFFFFFFFF when it is in none.
+ * Two calls on one cloud write the same bytes (sizes are integer sums, the numbering is a stable sort).
+ * Position3D not stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE; interleaved or columnar, owned, sliced or external, at any byte offset.
+ * tolerance not finite, not > 0 or with tolerance * tolerance not a normal number, min_size == 0, min_size > max_size ->
+ * PST_ERR_INVALID_ARGUMENT; 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED (so is a cloud whose finite extent overflows f64).  Null
+ * arguments and invalid parameters are answered before a device is looked for, the cloud's length after it; without a device the call is
+ * PST_ERR_NO_DEVICE, never a CPU path.  Any length from 0 up is legal: an empty cloud has no clusters (answered on the host).
+ * Cost: every point tests the points of its own and the neighbouring grid cells (cell edge just above the tolerance), about 27 x the mean
+ * cell occupancy / 2 pair tests per point -- a tolerance far above the point spacing is quadratic per cell. */
+/* Synchronous.  labels: len x uint32 in device memory (labels_memkind = PST_MEM_DEVICE) or host memory (anything else), the convention of
+ * the outlier masks.  sizes (host, nullable): sizes[c] = points of kept cluster c, when the kept clusters fit sizes_capacity; more kept
+ * clusters than that -> PST_ERR_RANGE with *n_clusters and *n_clustered set and the labels written (the pst_plane_inliers convention).
+ * *n_clusters = kept clusters, *n_clustered = points that carry a label (the sum of the kept sizes). */
+int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_size, uint64_t max_size, uint32_t* labels, uint32_t labels_memkind,
+                           uint64_t* sizes, size_t sizes_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+/* d_mask[i] = 1 iff first_cluster <= d_labels[i] < first_cluster + cluster_count, else 0 (computed without wrapping: 0xFFFFFFFF, "no
+ * cluster", is never selected).  Both arrays in DEVICE memory, n elements; stream-ordered, no host synchronisation: the mask is what
+ * pst_buffer_filter_into(..., PST_MEM_DEVICE, ...) takes. */
+int pst_cluster_mask_device(const uint32_t* d_labels, uint64_t n, uint32_t first_cluster, uint32_t cluster_count, uint8_t* d_mask);
+/* The traversal kernel's seams (tests place their sizes around them; each pointer optional): points one workgroup owns (one lane each), points
+ * of one LDS candidate tile -- 0: the kernel reads its candidates from the sorted position arrays directly and stages none.  Host only. */
+int pst_cluster_kernel_shape(uint32_t* points_per_block, uint32_t* tile_points);
+/* Measurement aid.  With PST_CLUSTER_TIMES=1 in the environment pst_euclidean_clusters brackets its three phases with stream events; this
+ * returns the calling thread's last call: ms = {index build (AABB, keys, sort, gather), traversal + union, bookkeeping}.  Zeros without the
+ * switch.  Host only. */
+int pst_cluster_phase_times(double ms[3]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -194,6 +194,10 @@ _PRODUCT_SIGNATURES = {
     "statistical_outlier_mask": [_P, _SZ, C.c_double, _P, C.c_uint32, _P, _D3, _U64P],
     "radius_outlier_mask": [_P, C.c_double, _SZ, _P, C.c_uint32, _U64P],
     "outlier_kernel_shape": [_U32P, _U32P, _U32P],
+    "euclidean_clusters": [_P, C.c_double, C.c_uint64, C.c_uint64, _P, C.c_uint32, _U64P, _SZ, _U64P, _U64P],
+    "cluster_mask_device": [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P],
+    "cluster_kernel_shape": [_U32P, _U32P],
+    "cluster_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

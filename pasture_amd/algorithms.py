@@ -425,3 +425,66 @@ def outlier_kernel_shape(api=None) -> dict:
     v = [C.c_uint32() for _ in range(3)]
     (api or product_api()).outlier_kernel_shape(*[C.byref(x) for x in v])
     return dict(zip(("points_per_block", "reduce_block", "reduce_points_per_block"), (x.value for x in v)))
+
+
+# ---- Euclidean cluster extraction (include/pasture_amd.h) ------------------------------------------------------------------------------------
+
+NO_CLUSTER = 0xFFFFFFFF
+_MAX_SIZE = 2 ** 64 - 1
+
+
+def euclidean_clusters(buffer: _Buffer, tolerance: float, min_size: int = 1, max_size: int = _MAX_SIZE, device_labels_ptr: Optional[int] = None):
+    """PCL's EuclideanClusterExtraction / PDAL's filters.cluster on the device: connected components of "closer than `tolerance`" over the
+    finite points, those of min_size .. max_size points kept and numbered by descending size (ties: ascending smallest member index).
+    Returns (labels, sizes): labels is a numpy uint32 array (NO_CLUSTER = 0xFFFFFFFF where a point is in no kept cluster), or None when the
+    len(buffer) uint32 values went to DEVICE memory at device_labels_ptr; sizes is a numpy uint64 array, sizes[c] = points of cluster c.
+    Two calls: the first writes the labels and reports the number of clusters, the second fetches that many sizes."""
+    n = buffer.len()
+    labels = np.full(n, NO_CLUSTER, dtype=np.uint32) if device_labels_ptr is None else None
+    ptr = C.c_void_p(int(device_labels_ptr) or None) if labels is None else C.c_void_p(labels.ctypes.data if n else 1)
+    kind = 0 if labels is None else 1
+    count, clustered = C.c_uint64(), C.c_uint64()
+    call = buffer.api.euclidean_clusters
+    call(buffer._h, tolerance, min_size, max_size, ptr, kind, None, 0, C.byref(count), C.byref(clustered))
+    sizes = np.zeros(count.value, dtype=np.uint64)
+    if count.value:
+        call(buffer._h, tolerance, min_size, max_size, ptr, kind, _u64(sizes), count.value, C.byref(count), C.byref(clustered))
+    return labels, sizes
+
+
+def cluster_mask(device_labels_ptr: int, n: int, first_cluster: int, cluster_count: int, device_mask_ptr: int, api=None) -> None:
+    """Stream-ordered: mask[i] = 1 iff first_cluster <= labels[i] < first_cluster + cluster_count, both arrays (n uint32 / n bytes) in DEVICE
+    memory -- the mask filter / filter_into take as (device_mask_ptr, 'device').  NO_CLUSTER is never selected."""
+    from ._capi import product_api
+    (api or product_api()).cluster_mask_device(C.c_void_p(int(device_labels_ptr) or None), n, first_cluster, cluster_count, C.c_void_p(int(device_mask_ptr) or None))
+
+
+def extract_clusters(buffer: _Buffer, tolerance: float, min_size: int = 1, max_size: int = _MAX_SIZE, first_cluster: int = 0, cluster_count: int = 1,
+                     out_buffer_type=None):
+    """(the points of clusters first_cluster .. first_cluster + cluster_count - 1 in buffer order with all their attributes, sizes of ALL kept
+    clusters): labels and mask stay in device memory.  `buffer` is columnar (filter is defined on HashMapBuffer)."""
+    from .layout import PointAttributeDataType as T
+    labels = _DeviceArray(buffer.api, T.U32, buffer.len())
+
+    def fill(mask_ptr):
+        sizes = euclidean_clusters(buffer, tolerance, min_size, max_size, device_labels_ptr=labels.ptr or 1)[1]
+        cluster_mask(labels.ptr, buffer.len(), first_cluster, cluster_count, mask_ptr, api=buffer.api)
+        return sizes
+    return _filter_by_device_mask(buffer, out_buffer_type, fill)
+
+
+def cluster_kernel_shape(api=None) -> dict:
+    """The seams of the traversal kernel: points one workgroup owns, points of one LDS candidate tile (0: candidates are not staged)."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).cluster_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "tile_points"), (x.value for x in v)))
+
+
+def cluster_phase_times(api=None):
+    """(index build, traversal + union, bookkeeping) in milliseconds of this thread's last euclidean_clusters call; zeros unless
+    PST_CLUSTER_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).cluster_phase_times(ms)
+    return tuple(ms)

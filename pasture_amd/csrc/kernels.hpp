@@ -210,4 +210,31 @@ bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stdd
 bool outlier_radius_mask(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record,
                          uint8_t* mask_dev, hipStream_t stream);
 
+// Euclidean cluster extraction (clusters.hip; the pipeline and its scratch are laid out in clusters_api.cpp).  The seams (pst_cluster_kernel_shape):
+constexpr uint32_t kClusterPointsPerBlock = 256;  // points one workgroup of the traversal kernel owns, one lane each
+constexpr uint32_t kClusterTilePoints = 0;        // points of an LDS candidate tile: none, the candidates are read from the sorted arrays
+// the device-side record of one call (64 bytes): the AABB of the finite points in the order-preserving integer encoding, their number, the
+// points that carry a label
+struct ClusterRecord { unsigned long long min_ordered[3], max_ordered[3], finite_count, clustered; };
+double cluster_decode_ordered(unsigned long long v);
+// cell = trunc((v - min) / edge) per axis, dim cells and `bits` key bits per axis (x lowest); every key is below 2^(bits[0] + bits[1] + bits[2])
+struct ClusterGrid { double min[3]; double edge; uint32_t dim[3]; uint32_t bits[3]; };
+bool cluster_bounds(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, ClusterRecord* rec, hipStream_t stream);
+// keys[i] = cell key of point i (all ones: not finite), vals[i] = i
+bool cluster_keys(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
+// gather (positions of the nf finite points in sorted order, parent[s] = s; `gathered`, optional, is recorded behind it), then traversal + union
+bool cluster_components(const uint8_t* pos_base, uint64_t pos_stride, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order,
+                        uint32_t nf, double* xs, double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered = nullptr);
+// root, size and smallest buffer index per component; flags[i] = 1 and root_at[i] = root where i is the smallest member of a kept component
+// (flags: n + 1 elements, the last one 0); the record's `clustered`
+bool cluster_flag_kept(uint32_t* parent, const uint32_t* order, uint64_t n, uint32_t nf, uint64_t min_size, uint64_t max_size, uint32_t* root, uint32_t* size,
+                       uint32_t* min_index, uint32_t* flags, uint32_t* root_at, ClusterRecord* rec, hipStream_t stream);
+// offsets = exclusive sum of flags: list_keys[offsets[i]] = 0xFFFFFFFF - size, list_roots[offsets[i]] = root of every flagged i
+bool cluster_list_kept(const uint32_t* flags, const unsigned long long* offsets, const uint32_t* root_at, const uint32_t* size, uint64_t n, uint32_t* list_keys,
+                       uint32_t* list_roots, hipStream_t stream);
+// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[order[s]] = rank of s's root, 0xFFFFFFFF without one
+bool cluster_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* order, const uint32_t* root, uint64_t n, uint32_t nf,
+                    uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, hipStream_t stream);
+bool cluster_mask(const uint32_t* labels, uint64_t n, uint32_t first_cluster, uint32_t cluster_count, uint8_t* mask, hipStream_t stream);
+
 }  // namespace pstk
