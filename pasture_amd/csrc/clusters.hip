@@ -28,8 +28,7 @@
 // no lane ever waits for another lane's write.  The parent reads inside the kernel are agent-scope relaxed loads; a read that is stale (the
 // XCDs' L2s are not coherent) still returns a former parent, which is a member of the same set with a lower id, so it costs steps, never
 // correctness: only the CAS decides who is a root, and it executes at the memory side.
-#include "device_common.hpp"
-#include "kernels.hpp"
+#include "positions_device.hpp"
 
 using namespace pstd;
 
@@ -40,15 +39,8 @@ namespace {
 constexpr uint32_t kP = pstk::kClusterPointsPerBlock;
 constexpr uint32_t kBoundsPoints = 1024;  // points per workgroup of the bounds fold, four per lane
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr double kInf = __builtin_huge_val();
 static_assert(kP == kBlock, "one lane per point");
 
-struct Pos { cgptr_t base; uint64_t stride; };
-__device__ __forceinline__ void load_point(const Pos& p, uint64_t i, double& x, double& y, double& z) {
-  cgptr_t q = p.base + i * p.stride;  // a packed record puts the Vec3f64 at any byte offset
-  x = load_un<double>(q); y = load_un<double>(q + 8); z = load_un<double>(q + 16);
-}
-__device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) < kInf; }  // false for a NaN
 // order-preserving map of the finite doubles onto unsigned integers (-0.0 below +0.0)
 __device__ __forceinline__ unsigned long long ordered(double v) {
   const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
@@ -241,18 +233,15 @@ __global__ __launch_bounds__(kBlock) void cluster_mask_kernel(const uint32_t* __
   mask[i] = (l != kNone && l >= first && l - first < count) ? 1 : 0;  // l - first cannot wrap behind l >= first
 }
 
-inline unsigned blocks_of(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }
-inline bool launched() { return hipGetLastError() == hipSuccess; }
-
 }  // namespace
 
 namespace pstk {
 
-bool cluster_bounds(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, ClusterRecord* rec, hipStream_t stream) {
+bool cluster_bounds(const Positions& pos, ClusterRecord* rec, hipStream_t stream) {
   // min: all ones, max / counts: zero -- the identities of the ordered encoding
   if (hipMemsetAsync(rec, 0, sizeof(ClusterRecord), stream) != hipSuccess || hipMemsetAsync(rec->min_ordered, 0xFF, sizeof(rec->min_ordered), stream) != hipSuccess)
     return false;
-  hipLaunchKernelGGL(cluster_bounds_kernel, dim3(blocks_of(n, kBoundsPoints)), dim3(kBlock), 0, stream, Pos{(cgptr_t)pos_base, pos_stride}, n, rec);
+  hipLaunchKernelGGL(cluster_bounds_kernel, dim3(blocks_of(pos.n, kBoundsPoints)), dim3(kBlock), 0, stream, pos_of(pos), pos.n, rec);
   return launched();
 }
 
@@ -261,14 +250,14 @@ double cluster_decode_ordered(unsigned long long v) {
   return __builtin_bit_cast(double, u);
 }
 
-bool cluster_keys(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream) {
-  hipLaunchKernelGGL(cluster_key_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, Pos{(cgptr_t)pos_base, pos_stride}, n, g, keys, vals);
+bool cluster_keys(const Positions& pos, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream) {
+  hipLaunchKernelGGL(cluster_key_kernel, dim3(blocks_of(pos.n, kBlock)), dim3(kBlock), 0, stream, pos_of(pos), pos.n, g, keys, vals);
   return launched();
 }
 
-bool cluster_components(const uint8_t* pos_base, uint64_t pos_stride, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order,
-                        uint32_t nf, double* xs, double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered) {
-  hipLaunchKernelGGL(cluster_gather_kernel, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, Pos{(cgptr_t)pos_base, pos_stride}, order, nf, xs, ys, zs, parent);
+bool cluster_components(const Positions& pos, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order, uint32_t nf, double* xs,
+                        double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered) {
+  hipLaunchKernelGGL(cluster_gather_kernel, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, pos_of(pos), order, nf, xs, ys, zs, parent);
   if (gathered && hipEventRecord(gathered, stream) != hipSuccess) return false;
   hipLaunchKernelGGL(cluster_traverse_kernel, dim3(blocks_of(nf, kP)), dim3(kBlock), 0, stream, sorted_keys, (const double*)xs, (const double*)ys, (const double*)zs, nf, g,
                      t2, parent);

@@ -2,6 +2,7 @@
 // launches of clusters.hip (where the definitions and the argument for the grid's margin are).
 #include <cmath>
 #include <cstring>
+#include <utility>
 
 #include "device_sort.hpp"
 #include "runtime.hpp"
@@ -11,15 +12,6 @@ using namespace pst;
 namespace {
 
 constexpr uint32_t kMaxCellsPerAxis = (1u << 21) - 1;  // 21 key bits per axis: 63 in all, and one more bit tells the all-ones key apart
-
-struct Scratch {
-  pstk::DevBuf buf;
-  uint8_t* get(size_t bytes, hipStream_t s) {
-    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure("pst_euclidean_clusters: scratch allocation failed: ");
-    return (uint8_t*)buf.p;
-  }
-};
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 uint32_t bits_for(uint32_t cells) {  // key bits that hold the cell numbers 0 .. cells - 1
   uint32_t b = 0;
@@ -125,8 +117,7 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   if (n == 0) return PST_OK;  // no points, no clusters, no labels to write
 
   hipStream_t s = current_stream();
-  const AttrView view = attr_view(*b, pm);
-  const uint8_t* pos = (const uint8_t*)(uintptr_t)view.addr;
+  const pstk::Positions pos = positions_of(*b, *pm);
   const bool labels_on_device = labels_memkind == PST_MEM_DEVICE;
 
   // One block of scratch.  The sort's input pair and the sorted positions are dead once the traversal has run; the bookkeeping lives in them:
@@ -142,27 +133,29 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, n + 1, s));
   const size_t tmp_bytes = std::max(sort64_bytes, std::max(sort32_bytes, scan_bytes));
   const size_t b4 = up256((n + 1) * 4), b8 = 2 * b4;  // an 8-byte array's room is exactly two 4-byte arrays' (the halves are used as such)
-  const size_t off_keys_b = b8, off_vals_a = 2 * b8, off_order = off_vals_a + b4, off_xs = off_order + b4, off_ys = off_xs + b8, off_zs = off_ys + b8;
-  const size_t off_parent = off_zs + b8, off_offsets = off_parent + b4, off_rec = off_offsets + b8, off_tmp = off_rec + 256, off_labels = off_tmp + up256(tmp_bytes);
-  Scratch scratch;
-  uint8_t* base = scratch.get(off_labels + (labels_on_device ? 0 : b4), s);
-  uint64_t* keys_a = (uint64_t*)base;
-  uint64_t* keys_b = (uint64_t*)(base + off_keys_b);
-  uint32_t* vals_a = (uint32_t*)(base + off_vals_a);
-  uint32_t* order = (uint32_t*)(base + off_order);
-  double* xs = (double*)(base + off_xs);
-  double* ys = (double*)(base + off_ys);
-  double* zs = (double*)(base + off_zs);
-  uint32_t* parent = (uint32_t*)(base + off_parent);
-  unsigned long long* offsets = (unsigned long long*)(base + off_offsets);
-  pstk::ClusterRecord* rec = (pstk::ClusterRecord*)(base + off_rec);
-  void* tmp = base + off_tmp;
-  uint32_t* labels_dev = labels_on_device ? labels : (uint32_t*)(base + off_labels);
+  const auto halves = [b4](void* p) { return std::pair<uint32_t*, uint32_t*>{(uint32_t*)p, (uint32_t*)((uint8_t*)p + b4)}; };
+  ScratchLayout layout;
+  const size_t off_keys_a = layout.add(b8), off_keys_b = layout.add(b8), off_vals_a = layout.add(b4), off_order = layout.add(b4);
+  const size_t off_xs = layout.add(b8), off_ys = layout.add(b8), off_zs = layout.add(b8), off_parent = layout.add(b4), off_offsets = layout.add(b8);
+  const size_t off_rec = layout.add(256), off_tmp = layout.add(tmp_bytes), off_labels = layout.add(labels_on_device ? 0 : b4);
+  Scratch scratch(layout, s, who.c_str());
+  uint64_t* keys_a = scratch.at<uint64_t>(off_keys_a);
+  uint64_t* keys_b = scratch.at<uint64_t>(off_keys_b);
+  uint32_t* vals_a = scratch.at<uint32_t>(off_vals_a);
+  uint32_t* order = scratch.at<uint32_t>(off_order);
+  double* xs = scratch.at<double>(off_xs);
+  double* ys = scratch.at<double>(off_ys);
+  double* zs = scratch.at<double>(off_zs);
+  uint32_t* parent = scratch.at<uint32_t>(off_parent);
+  unsigned long long* offsets = scratch.at<unsigned long long>(off_offsets);
+  pstk::ClusterRecord* rec = scratch.at<pstk::ClusterRecord>(off_rec);
+  void* tmp = scratch.at<void>(off_tmp);
+  uint32_t* labels_dev = labels_on_device ? labels : scratch.at<uint32_t>(off_labels);
 
   PhaseEvents events;
   events.mark(0, s);
   // ---- index build: AABB of the finite points -> (host: grid) -> keys -> sort -> gather
-  if (!pstk::cluster_bounds(pos, view.stride, n, rec, s)) throw hip_failure("cluster bounds launch failed: ");
+  if (!pstk::cluster_bounds(pos, rec, s)) throw hip_failure("cluster bounds launch failed: ");
   pstk::ClusterRecord r{};
   PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
   stream_sync(s);
@@ -175,23 +168,19 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   }
   const pstk::ClusterGrid grid = make_grid(r, tolerance);
   const unsigned key_bits = grid.bits[0] + grid.bits[1] + grid.bits[2];
-  if (!pstk::cluster_keys(pos, view.stride, n, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure("cluster key launch failed: ");
+  if (!pstk::cluster_keys(pos, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure("cluster key launch failed: ");
   size_t bytes = tmp_bytes;
   PST_HIP_CHECK(pstk::sort_pairs_u64(tmp, bytes, keys_a, keys_b, vals_a, order, n, key_bits + 1, s));
   // ---- traversal + union
-  if (!pstk::cluster_components(pos, view.stride, grid, t2, (const unsigned long long*)keys_b, order, nf, xs, ys, zs, parent, s, events.on ? events.e[1] : nullptr))
+  if (!pstk::cluster_components(pos, grid, t2, (const unsigned long long*)keys_b, order, nf, xs, ys, zs, parent, s, events.on ? events.e[1] : nullptr))
     throw hip_failure("cluster traversal launch failed: ");
   events.mark(2, s);
   // ---- bookkeeping
-  uint32_t* root = (uint32_t*)xs;
-  uint32_t* size = (uint32_t*)((uint8_t*)xs + b4);
-  uint32_t* min_index = (uint32_t*)ys;
-  uint32_t* root_at = (uint32_t*)((uint8_t*)ys + b4);
-  uint32_t* flags = (uint32_t*)zs;
-  uint32_t* list_keys = (uint32_t*)keys_a;
-  uint32_t* list_roots = (uint32_t*)((uint8_t*)keys_a + b4);
-  uint32_t* sorted_keys = (uint32_t*)keys_b;
-  uint32_t* sorted_roots = (uint32_t*)((uint8_t*)keys_b + b4);
+  const auto [root, size] = halves(xs);
+  const auto [min_index, root_at] = halves(ys);
+  uint32_t* flags = halves(zs).first;
+  const auto [list_keys, list_roots] = halves(keys_a);
+  const auto [sorted_keys, sorted_roots] = halves(keys_b);
   uint32_t* rank_of_root = vals_a;
   if (!pstk::cluster_flag_kept(parent, order, n, nf, min_size, max_size, root, size, min_index, flags, root_at, rec, s)) throw hip_failure("cluster flatten launch failed: ");
   bytes = tmp_bytes;

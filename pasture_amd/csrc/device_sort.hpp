@@ -1,4 +1,5 @@
-// Sorts and scans shared by the spatial-index builders (normals.hip, voxel.hip): the library's own kernels (radix_sort.hip).  Every function follows
+// Sorts and scans shared by the spatial-index builders (normals.hip, voxel.hip) and by the RANSAC, outlier and cluster entry points (ransac_api.cpp,
+// outliers_api.cpp, clusters_api.cpp; their scratch is a DevBuf through pst::Scratch): the library's own kernels (radix_sort.hip).  Every function follows
 // the two-call convention: tmp == nullptr writes the scratch size to `bytes` and does nothing else.  All of them are stream-ordered; none synchronises.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -64,6 +64,9 @@ size_t minmax_partials_bytes();
 void launch_minmax(const uint8_t* base, uint64_t stride, uint64_t n, uint32_t ct, uint32_t ncomp, bool acc_f64, void* partials,
                    void* out, hipStream_t stream);
 
+// Where a call's positions are: Vec3f64 at base + i * stride, for n points (pst::positions_of makes it; kernels read it through positions_device.hpp)
+struct Positions { const uint8_t* base; uint64_t stride; uint64_t n; };
+
 // compute_centroid (normal_estimation.rs:198-237): per-block records {sum xyz over all points, sum xyz over the finite points, finite count,
 // NaN seen} of Vec3f64 values at base + e * stride; returns the number of records written to `partials` (centroid_partials_bytes())
 size_t centroid_partials_bytes();
@@ -183,15 +186,14 @@ constexpr uint32_t kRansacBatch = 1024;           // hypotheses scored per pass 
 size_t ransac_record_bytes(bool line);
 // table -> scoring (one pass over the positions per kRansacBatch hypotheses) -> arg-max.  recs: iterations records, rank: iterations u64,
 // out8: {best iteration, its ranking, model doubles x 6} (64 bytes).  samples_dev: iterations x 3 (plane) / x 2 (line) point indices.
-bool ransac_fit(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, double thr, const uint64_t* samples_dev, uint64_t iterations, void* recs,
-                unsigned long long* rank, unsigned long long* out8, hipStream_t stream);
+bool ransac_fit(bool line, const Positions& p, double thr, const uint64_t* samples_dev, uint64_t iterations, void* recs, unsigned long long* rank,
+                unsigned long long* out8, hipStream_t stream);
 // model: plane a b c d / line first xyz, second xyz.  rec_scratch: ransac_record_bytes() of device memory.
 bool ransac_model_record(bool line, const double* model, double thr, void* rec_scratch, hipStream_t stream);
-bool ransac_mask(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const double* model, double thr, void* rec_scratch, uint8_t* mask_dev,
-                 hipStream_t stream);
+bool ransac_mask(bool line, const Positions& p, const double* model, double thr, void* rec_scratch, uint8_t* mask_dev, hipStream_t stream);
 // write = false: counts[block] = inliers among the block's kRansacPointsPerBlock points; write = true: the indices, ascending, at offsets[block] ..
-bool ransac_index_pass(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const void* rec, uint32_t* counts, const unsigned long long* offsets,
-                       unsigned long long* indices, bool write, hipStream_t stream);
+bool ransac_index_pass(bool line, const Positions& p, const void* rec, uint32_t* counts, const unsigned long long* offsets, unsigned long long* indices, bool write,
+                       hipStream_t stream);
 
 // Neighbour distances and outlier masks over the kNN lists (outliers.hip).  The kernels' seams (pst_outlier_kernel_shape):
 constexpr uint32_t kOutlierPointsPerBlock = 64;   // a workgroup of the distance kernels owns the whole lists of this many points, whatever k
@@ -200,15 +202,14 @@ constexpr uint32_t kOutlierReducePoints = 1024;   // points per block partial of
 size_t outlier_record_bytes();                    // the result record: {mean, stddev, threshold, (double)m} as doubles, then the kept count (u64)
 size_t outlier_partials_bytes(uint64_t n);
 // knn_dev: uint32 [n][k] as run_normals writes them.  dist_dev: f64 [n][k]
-bool outlier_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, const uint32_t* knn_dev, double* dist_dev, hipStream_t stream);
+bool outlier_distances(const Positions& pos, uint32_t k, const uint32_t* knn_dev, double* dist_dev, hipStream_t stream);
 // dbar_dev[q] = (d[q][1] + ... + d[q][mean_k]) / mean_k, mean_k < k
-bool outlier_mean_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t mean_k, const uint32_t* knn_dev, double* dbar_dev,
-                            hipStream_t stream);
+bool outlier_mean_distances(const Positions& pos, uint32_t k, uint32_t mean_k, const uint32_t* knn_dev, double* dbar_dev, hipStream_t stream);
 // count and sum -> mean -> squared deviations -> stddev, threshold -> mask and kept count; partials: outlier_partials_bytes(n), record: outlier_record_bytes()
 bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stddev_mult, void* partials, void* record, uint8_t* mask_dev, hipStream_t stream);
 // mask[q] = d[q][slot] <= radius; the record's kept count
-bool outlier_radius_mask(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record,
-                         uint8_t* mask_dev, hipStream_t stream);
+bool outlier_radius_mask(const Positions& pos, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record, uint8_t* mask_dev,
+                         hipStream_t stream);
 
 // Euclidean cluster extraction (clusters.hip; the pipeline and its scratch are laid out in clusters_api.cpp).  The seams (pst_cluster_kernel_shape):
 constexpr uint32_t kClusterPointsPerBlock = 256;  // points one workgroup of the traversal kernel owns, one lane each
@@ -219,12 +220,13 @@ struct ClusterRecord { unsigned long long min_ordered[3], max_ordered[3], finite
 double cluster_decode_ordered(unsigned long long v);
 // cell = trunc((v - min) / edge) per axis, dim cells and `bits` key bits per axis (x lowest); every key is below 2^(bits[0] + bits[1] + bits[2])
 struct ClusterGrid { double min[3]; double edge; uint32_t dim[3]; uint32_t bits[3]; };
-bool cluster_bounds(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, ClusterRecord* rec, hipStream_t stream);
+bool cluster_bounds(const Positions& pos, ClusterRecord* rec, hipStream_t stream);
 // keys[i] = cell key of point i (all ones: not finite), vals[i] = i
-bool cluster_keys(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
+bool cluster_keys(const Positions& pos, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
 // gather (positions of the nf finite points in sorted order, parent[s] = s; `gathered`, optional, is recorded behind it), then traversal + union
-bool cluster_components(const uint8_t* pos_base, uint64_t pos_stride, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order,
-                        uint32_t nf, double* xs, double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered = nullptr);
+// (of `pos` only base and stride are used: the gather reads the nf points `order` names)
+bool cluster_components(const Positions& pos, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order, uint32_t nf, double* xs,
+                        double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered = nullptr);
 // root, size and smallest buffer index per component; flags[i] = 1 and root_at[i] = root where i is the smallest member of a kept component
 // (flags: n + 1 elements, the last one 0); the record's `clustered`
 bool cluster_flag_kept(uint32_t* parent, const uint32_t* order, uint64_t n, uint32_t nf, uint64_t min_size, uint64_t max_size, uint32_t* root, uint32_t* size,

@@ -16,8 +16,7 @@
 // block partials -- thread t the contiguous run [t * c, (t + 1) * c), c = ceil(blocks / kOutlierReduceBlock), in block order, then the same tree.
 // Nothing depends on anything but n: two calls on one cloud give the same bits.  No floating-point atomics; the kept count is an integer atomic
 // per wave of the mask kernels.
-#include "device_common.hpp"
-#include "kernels.hpp"
+#include "positions_device.hpp"
 
 using namespace pstd;
 
@@ -29,14 +28,8 @@ constexpr uint32_t kP = pstk::kOutlierPointsPerBlock;
 constexpr uint32_t kRP = pstk::kOutlierReducePoints;
 constexpr uint32_t kRB = pstk::kOutlierReduceBlock;
 constexpr uint32_t kNoIndex = 0xFFFFFFFFu;
-constexpr double kInf = __builtin_huge_val();
 static_assert(kRB == kBlock && kRP % kBlock == 0 && kP <= kBlock, "the reduction kernels are written for one kBlock workgroup");
 
-struct Pos { cgptr_t base; uint64_t stride; };
-__device__ __forceinline__ void load_point(const Pos& p, uint64_t i, double& x, double& y, double& z) {
-  cgptr_t q = p.base + i * p.stride;  // a packed record puts the Vec3f64 at any byte offset
-  x = load_un<double>(q); y = load_un<double>(q + 8); z = load_un<double>(q + 16);
-}
 __device__ __forceinline__ double slot_distance(const Pos& pos, uint64_t q, uint32_t j) {
   if (j == kNoIndex) return kInf;
   double qx, qy, qz, px, py, pz;
@@ -45,7 +38,6 @@ __device__ __forceinline__ double slot_distance(const Pos& pos, uint64_t q, uint
   const double dx = px - qx, dy = py - qy, dz = pz - qz;
   return __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
 }
-__device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) < kInf; }  // false for a NaN
 
 // the device-side result record of one call (64 bytes)
 struct Record { double mean, stddev, threshold, m; unsigned long long kept, finite_count; double sum, pad; };
@@ -174,8 +166,6 @@ __global__ __launch_bounds__(kBlock) void outlier_mask_kernel(const double* __re
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&rec->kept, c);
 }
 
-inline unsigned blocks_of(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 
 namespace pstk {
@@ -183,18 +173,17 @@ namespace pstk {
 size_t outlier_record_bytes() { return sizeof(Record); }
 size_t outlier_partials_bytes(uint64_t n) { return (size_t)blocks_of(n, kRP) * 16; }
 
-bool outlier_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, const uint32_t* knn_dev, double* dist_dev, hipStream_t stream) {
-  if (n == 0) return true;
-  hipLaunchKernelGGL(outlier_distance_kernel<false>, dim3(blocks_of(n, kP)), dim3(kBlock), 0, stream, Pos{(cgptr_t)pos_base, pos_stride}, n, k, 0u, knn_dev, dist_dev);
-  return hipGetLastError() == hipSuccess;
+bool outlier_distances(const Positions& pos, uint32_t k, const uint32_t* knn_dev, double* dist_dev, hipStream_t stream) {
+  if (pos.n == 0) return true;
+  hipLaunchKernelGGL(outlier_distance_kernel<false>, dim3(blocks_of(pos.n, kP)), dim3(kBlock), 0, stream, pos_of(pos), pos.n, k, 0u, knn_dev, dist_dev);
+  return launched();
 }
 
-bool outlier_mean_distances(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t mean_k, const uint32_t* knn_dev, double* dbar_dev,
-                            hipStream_t stream) {
-  if (n == 0) return true;
+bool outlier_mean_distances(const Positions& pos, uint32_t k, uint32_t mean_k, const uint32_t* knn_dev, double* dbar_dev, hipStream_t stream) {
+  if (pos.n == 0) return true;
   const size_t lds = (size_t)kP * (k | 1u) * sizeof(double);  // at most 64 * 65 * 8 = 33 280 bytes
-  hipLaunchKernelGGL(outlier_distance_kernel<true>, dim3(blocks_of(n, kP)), dim3(kBlock), lds, stream, Pos{(cgptr_t)pos_base, pos_stride}, n, k, mean_k, knn_dev, dbar_dev);
-  return hipGetLastError() == hipSuccess;
+  hipLaunchKernelGGL(outlier_distance_kernel<true>, dim3(blocks_of(pos.n, kP)), dim3(kBlock), lds, stream, pos_of(pos), pos.n, k, mean_k, knn_dev, dbar_dev);
+  return launched();
 }
 
 bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stddev_mult, void* partials, void* record, uint8_t* mask_dev, hipStream_t stream) {
@@ -207,15 +196,15 @@ bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stdd
   hipLaunchKernelGGL(outlier_partial_kernel<1>, dim3(blocks), dim3(kBlock), 0, stream, dbar_dev, n, (const Record*)rec, psum, pcount);
   hipLaunchKernelGGL(outlier_final_kernel<1>, dim3(1), dim3(kBlock), 0, stream, (const double*)psum, (const unsigned long long*)pcount, (uint64_t)blocks, stddev_mult, rec);
   hipLaunchKernelGGL(outlier_mask_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, dbar_dev, n, mask_dev, rec);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
-bool outlier_radius_mask(const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record,
-                         uint8_t* mask_dev, hipStream_t stream) {
+bool outlier_radius_mask(const Positions& pos, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record, uint8_t* mask_dev,
+                         hipStream_t stream) {
   if (hipMemsetAsync(record, 0, sizeof(Record), stream) != hipSuccess) return false;
-  hipLaunchKernelGGL(outlier_radius_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, Pos{(cgptr_t)pos_base, pos_stride}, n, k, slot, radius, knn_dev, mask_dev,
+  hipLaunchKernelGGL(outlier_radius_kernel, dim3(blocks_of(pos.n, kBlock)), dim3(kBlock), 0, stream, pos_of(pos), pos.n, k, slot, radius, knn_dev, mask_dev,
                      (Record*)record);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
 }  // namespace pstk

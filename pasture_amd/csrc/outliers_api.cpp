@@ -9,8 +9,6 @@ using namespace pst;
 
 namespace {
 
-struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };
-
 // The checks of pst_compute_normals_device in two halves: what the arguments and the layout alone decide is answered before a device is looked
 // for, the cloud's length after it (so a call without a device is PST_ERR_NO_DEVICE whatever the buffer holds).
 const Member& checked_arguments(const pst_buffer& b, size_t k, const char* who) {
@@ -26,26 +24,12 @@ void checked_length(const pst_buffer& b, size_t at_least, const char* who) {
   if (b.len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
 }
 
-PosView position_view(const pst_buffer& b, const Member& m) {
-  const AttrView v = attr_view(b, &m);
-  return PosView{(const uint8_t*)(uintptr_t)v.addr, v.stride, b.len};
-}
-
 // the neighbour lists only; degenerate plane fits (a positive return) are no error here: the lists are written whatever the fit says
-void search(const PosView& pv, size_t k, uint32_t* d_knn, hipStream_t s, const char* who) {
+void search(const pstk::Positions& pv, size_t k, uint32_t* d_knn, hipStream_t s, const char* who) {
   const long long rc = pstk::run_normals(pv.base, pv.stride, pv.n, (uint32_t)k, nullptr, nullptr, nullptr, d_knn, 0, 0, 0, 0, s);
   if (rc == -2) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
   if (rc < 0) throw hip_failure(std::string(who) + ": neighbour search failed: ");
 }
-
-struct Scratch {
-  pstk::DevBuf buf;
-  uint8_t* get(size_t bytes, hipStream_t s, const char* who) {
-    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure(std::string(who) + ": scratch allocation failed: ");
-    return (uint8_t*)buf.p;
-  }
-};
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 void check_mask_args(const uint8_t* mask, uint32_t mask_memkind, const uint64_t* kept) {
   not_null(mask, "mask");
@@ -75,11 +59,11 @@ int pst_knn_search_device(const pst_buffer* b, size_t k, uint32_t* d_knn, double
   ensure_device();
   checked_length(*b, 3, who);
   hipStream_t s = current_stream();
-  const PosView pv = position_view(*b, pm);
+  const pstk::Positions pv = positions_of(*b, pm);
   Scratch own;
-  if (!d_knn) d_knn = (uint32_t*)own.get(pv.n * k * sizeof(uint32_t), s, who);
+  if (!d_knn) d_knn = own.alloc<uint32_t>(pv.n * k * sizeof(uint32_t), s, who);
   search(pv, k, d_knn, s, who);
-  if (!pstk::outlier_distances(pv.base, pv.stride, pv.n, (uint32_t)k, d_knn, d_dist, s)) throw hip_failure("knn_search: distance launch failed: ");
+  if (!pstk::outlier_distances(pv, (uint32_t)k, d_knn, d_dist, s)) throw hip_failure("knn_search: distance launch failed: ");
   stream_sync(s);
   PST_API_END
 }
@@ -98,25 +82,25 @@ int pst_statistical_outlier_mask(const pst_buffer* b, size_t mean_k, double stdd
   ensure_device();
   checked_length(*b, mean_k + 1, who);
   hipStream_t s = current_stream();
-  const PosView pv = position_view(*b, pm);
+  const pstk::Positions pv = positions_of(*b, pm);
   const size_t n = pv.n;
   const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
   // one block of scratch: neighbour lists | dbar (unless the caller takes it) | block partials | result record | mask (host masks)
-  const size_t off_dbar = up256(n * k * sizeof(uint32_t));
-  const size_t off_part = off_dbar + (d_mean_dist ? 0 : up256(n * sizeof(double)));
-  const size_t off_rec = off_part + up256(pstk::outlier_partials_bytes(n));
-  const size_t off_mask = off_rec + up256(pstk::outlier_record_bytes());
-  Scratch scratch;
-  uint8_t* base = scratch.get(off_mask + (mask_on_device ? 0 : n), s, who);
-  uint32_t* d_knn = (uint32_t*)base;
-  double* dbar = d_mean_dist ? d_mean_dist : (double*)(base + off_dbar);
-  uint8_t* mask_dev = mask_on_device ? mask : base + off_mask;
+  ScratchLayout layout;
+  const size_t off_knn = layout.add(n * k * sizeof(uint32_t)), off_dbar = layout.add(d_mean_dist ? 0 : n * sizeof(double));
+  const size_t off_part = layout.add(pstk::outlier_partials_bytes(n)), off_rec = layout.add(pstk::outlier_record_bytes());
+  const size_t off_mask = layout.add(mask_on_device ? 0 : n);
+  Scratch scratch(layout, s, who);
+  uint32_t* d_knn = scratch.at<uint32_t>(off_knn);
+  double* dbar = d_mean_dist ? d_mean_dist : scratch.at<double>(off_dbar);
+  void* rec = scratch.at<void>(off_rec);
+  uint8_t* mask_dev = mask_on_device ? mask : scratch.at<uint8_t>(off_mask);
   search(pv, k, d_knn, s, who);
-  if (!pstk::outlier_mean_distances(pv.base, pv.stride, n, (uint32_t)k, (uint32_t)mean_k, d_knn, dbar, s) ||
-      !pstk::outlier_statistics_and_mask(dbar, n, stddev_mult, base + off_part, base + off_rec, mask_dev, s))
+  if (!pstk::outlier_mean_distances(pv, (uint32_t)k, (uint32_t)mean_k, d_knn, dbar, s) ||
+      !pstk::outlier_statistics_and_mask(dbar, n, stddev_mult, scratch.at<void>(off_part), rec, mask_dev, s))
     throw hip_failure("statistical outlier launch failed: ");
   HostRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_rec, sizeof(r), hipMemcpyDeviceToHost, s));
+  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
   if (!mask_on_device) PST_HIP_CHECK(hipMemcpyAsync(mask, mask_dev, n, hipMemcpyDeviceToHost, s));
   stream_sync(s);
   for (int i = 0; i < 4; ++i) stats[i] = r.stats[i];
@@ -136,20 +120,19 @@ int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neigh
   ensure_device();
   checked_length(*b, 3, who);
   hipStream_t s = current_stream();
-  const PosView pv = position_view(*b, pm);
+  const pstk::Positions pv = positions_of(*b, pm);
   const size_t n = pv.n;
   const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
-  const size_t off_rec = up256(n * k * sizeof(uint32_t));
-  const size_t off_mask = off_rec + up256(pstk::outlier_record_bytes());
-  Scratch scratch;
-  uint8_t* base = scratch.get(off_mask + (mask_on_device ? 0 : n), s, who);
-  uint32_t* d_knn = (uint32_t*)base;
-  uint8_t* mask_dev = mask_on_device ? mask : base + off_mask;
+  ScratchLayout layout;  // neighbour lists | result record | mask (host masks)
+  const size_t off_knn = layout.add(n * k * sizeof(uint32_t)), off_rec = layout.add(pstk::outlier_record_bytes()), off_mask = layout.add(mask_on_device ? 0 : n);
+  Scratch scratch(layout, s, who);
+  uint32_t* d_knn = scratch.at<uint32_t>(off_knn);
+  void* rec = scratch.at<void>(off_rec);
+  uint8_t* mask_dev = mask_on_device ? mask : scratch.at<uint8_t>(off_mask);
   search(pv, k, d_knn, s, who);
-  if (!pstk::outlier_radius_mask(pv.base, pv.stride, n, (uint32_t)k, (uint32_t)min_neighbours, radius, d_knn, base + off_rec, mask_dev, s))
-    throw hip_failure("radius outlier launch failed: ");
+  if (!pstk::outlier_radius_mask(pv, (uint32_t)k, (uint32_t)min_neighbours, radius, d_knn, rec, mask_dev, s)) throw hip_failure("radius outlier launch failed: ");
   HostRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_rec, sizeof(r), hipMemcpyDeviceToHost, s));
+  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
   if (!mask_on_device) PST_HIP_CHECK(hipMemcpyAsync(mask, mask_dev, n, hipMemcpyDeviceToHost, s));
   stream_sync(s);
   *kept = r.kept;

@@ -20,9 +20,8 @@
 // The line compares s = (cr.x^2 + cr.y^2) + cr.z^2 -- the very value the reference takes the root of -- with lo2 = fl(fl(t*t) * (1 - 2^-38)) and
 // hi2 = fl(fl(t*t) * (1 + 2^-38)), t = fl(thr * len): lo2 <= (thr*len)^2 * (1 - 2^-38) * (1 + u)^4, so s < lo2 gives sqrt(s) < thr*len*(1 - 2^-39 + 2^-51),
 // fl(sqrt(s)) <= that * (1 + u), and the quotient by len stays below thr*(1 - 2^-40) < pred(thr); symmetric above.  Same arming rule, on t and t*t.
-#include "device_common.hpp"
 #include "device_sort.hpp"
-#include "kernels.hpp"
+#include "positions_device.hpp"
 
 #include <algorithm>
 
@@ -33,7 +32,6 @@ using namespace pstd;
 namespace {
 
 constexpr uint32_t kPointsPerLane = pstk::kRansacPointsPerWave / 64;
-constexpr double kInf = __builtin_huge_val();
 constexpr double kMinNormal = 2.2250738585072014e-308;
 
 struct PlaneRec { double a, b, c, d, e, lo, hi, thr; };                                  // 64 bytes
@@ -101,12 +99,6 @@ __device__ __forceinline__ bool inlier(const typename M::Rec& r, double x, doubl
   if (v < M::lo(r)) return true;
   if (v > M::hi(r)) return false;
   return M::exact(r, v);
-}
-
-struct Pos { cgptr_t base; uint64_t stride; };
-__device__ __forceinline__ void load_point(const Pos& p, uint64_t i, double& x, double& y, double& z) {
-  cgptr_t q = p.base + i * p.stride;  // a packed record puts the Vec3f64 at any byte offset
-  x = load_un<double>(q); y = load_un<double>(q + 8); z = load_un<double>(q + 16);
 }
 
 // ---- hypothesis table -----------------------------------------------------------------------------------------------------------------------
@@ -303,7 +295,7 @@ bool run_model_rec(const double* model, double thr, typename M::Rec* rec, hipStr
   for (int c = 0; c < nm; ++c) m.v[c] = model[c];
   if constexpr (std::is_same<M, PlaneModel>::value) hipLaunchKernelGGL(ransac_plane_model_kernel, dim3(1), dim3(1), 0, s, m, thr, rec);
   else hipLaunchKernelGGL(ransac_line_model_kernel, dim3(1), dim3(1), 0, s, m, thr, rec);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
 template <typename M, bool LINE>
@@ -314,16 +306,16 @@ bool fit(const Pos& pos, uint64_t n, double thr, const uint64_t* samples_dev, ui
   const unsigned tgrid = (unsigned)((iterations + kBlock - 1) / kBlock);
   if constexpr (LINE) hipLaunchKernelGGL(ransac_line_table_kernel, dim3(tgrid), dim3(kBlock), 0, s, pos, samples_dev, (uint32_t)iterations, thr, recs, rank);
   else hipLaunchKernelGGL(ransac_plane_table_kernel, dim3(tgrid), dim3(kBlock), 0, s, pos, samples_dev, (uint32_t)iterations, thr, recs, rank);
-  if (hipGetLastError() != hipSuccess) return false;
+  if (!launched()) return false;
   const uint64_t blocks_needed = (n + pstk::kRansacPointsPerBlock - 1) / pstk::kRansacPointsPerBlock;
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks_needed, (uint64_t)pstk::device_cus() * pstk::kRansacBlocksPerCu));
   for (uint64_t h0 = 0; h0 < iterations; h0 += pstk::kRansacBatch) {
     const uint32_t nh = (uint32_t)std::min<uint64_t>(pstk::kRansacBatch, iterations - h0);
     hipLaunchKernelGGL(ransac_score_kernel<M>, dim3(grid), dim3(kBlock), 0, s, pos, n, (const Rec*)(recs + h0), nh, rank + h0);
-    if (hipGetLastError() != hipSuccess) return false;
+    if (!launched()) return false;
   }
   hipLaunchKernelGGL((ransac_argmax_kernel<Rec, LINE>), dim3(1), dim3(kBlock), 0, s, rank, recs, iterations, out);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
 template <typename M>
@@ -333,7 +325,7 @@ bool mask(const Pos& pos, uint64_t n, const double* model, double thr, void* rec
   if (n == 0) return true;
   const unsigned grid = (unsigned)std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)pstk::device_cus() * 16);
   hipLaunchKernelGGL(ransac_mask_kernel<M>, dim3(grid), dim3(kBlock), 0, s, pos, n, (const Rec*)rec_scratch, mask_dev);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
 template <typename M>
@@ -343,7 +335,7 @@ bool index_pass(const Pos& pos, uint64_t n, const void* rec, uint32_t* counts, c
   const unsigned grid = (unsigned)((n + pstk::kRansacPointsPerBlock - 1) / pstk::kRansacPointsPerBlock);
   if (write) hipLaunchKernelGGL((ransac_index_kernel<M, true>), dim3(grid), dim3(kBlock), 0, s, pos, n, (const Rec*)rec, counts, offsets, indices);
   else hipLaunchKernelGGL((ransac_index_kernel<M, false>), dim3(grid), dim3(kBlock), 0, s, pos, n, (const Rec*)rec, counts, offsets, indices);
-  return hipGetLastError() == hipSuccess;
+  return launched();
 }
 
 }  // namespace
@@ -352,28 +344,24 @@ namespace pstk {
 
 size_t ransac_record_bytes(bool line) { return line ? sizeof(LineRec) : sizeof(PlaneRec); }
 
-bool ransac_fit(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, double thr, const uint64_t* samples_dev, uint64_t iterations, void* recs,
-                unsigned long long* rank, unsigned long long* out8, hipStream_t stream) {
-  const Pos pos{(cgptr_t)pos_base, pos_stride};
-  return line ? fit<LineModel, true>(pos, n, thr, samples_dev, iterations, recs, rank, out8, stream)
-              : fit<PlaneModel, false>(pos, n, thr, samples_dev, iterations, recs, rank, out8, stream);
+bool ransac_fit(bool line, const Positions& p, double thr, const uint64_t* samples_dev, uint64_t iterations, void* recs, unsigned long long* rank,
+                unsigned long long* out8, hipStream_t stream) {
+  return line ? fit<LineModel, true>(pos_of(p), p.n, thr, samples_dev, iterations, recs, rank, out8, stream)
+              : fit<PlaneModel, false>(pos_of(p), p.n, thr, samples_dev, iterations, recs, rank, out8, stream);
 }
 
-bool ransac_mask(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const double* model, double thr, void* rec_scratch, uint8_t* mask_dev,
-                 hipStream_t stream) {
-  const Pos pos{(cgptr_t)pos_base, pos_stride};
-  return line ? mask<LineModel>(pos, n, model, thr, rec_scratch, mask_dev, stream) : mask<PlaneModel>(pos, n, model, thr, rec_scratch, mask_dev, stream);
+bool ransac_mask(bool line, const Positions& p, const double* model, double thr, void* rec_scratch, uint8_t* mask_dev, hipStream_t stream) {
+  return line ? mask<LineModel>(pos_of(p), p.n, model, thr, rec_scratch, mask_dev, stream) : mask<PlaneModel>(pos_of(p), p.n, model, thr, rec_scratch, mask_dev, stream);
 }
 
 bool ransac_model_record(bool line, const double* model, double thr, void* rec_scratch, hipStream_t stream) {
   return line ? run_model_rec<LineModel>(model, thr, (LineRec*)rec_scratch, stream) : run_model_rec<PlaneModel>(model, thr, (PlaneRec*)rec_scratch, stream);
 }
 
-bool ransac_index_pass(bool line, const uint8_t* pos_base, uint64_t pos_stride, uint64_t n, const void* rec, uint32_t* counts, const unsigned long long* offsets,
-                       unsigned long long* indices, bool write, hipStream_t stream) {
-  const Pos pos{(cgptr_t)pos_base, pos_stride};
-  return line ? index_pass<LineModel>(pos, n, rec, counts, offsets, indices, write, stream)
-              : index_pass<PlaneModel>(pos, n, rec, counts, offsets, indices, write, stream);
+bool ransac_index_pass(bool line, const Positions& p, const void* rec, uint32_t* counts, const unsigned long long* offsets, unsigned long long* indices, bool write,
+                       hipStream_t stream) {
+  return line ? index_pass<LineModel>(pos_of(p), p.n, rec, counts, offsets, indices, write, stream)
+              : index_pass<PlaneModel>(pos_of(p), p.n, rec, counts, offsets, indices, write, stream);
 }
 
 }  // namespace pstk

@@ -38,31 +38,22 @@ void sample_indices(uint64_t seed, uint64_t n, size_t iterations, uint32_t per, 
   }
 }
 
-struct PosView { const uint8_t* base; uint64_t stride; uint64_t n; };  // an AttrView as the kernels take it, and the number of points
-
 const Member* position_member(const pst_buffer& b) {
   const Member* m = position_vec3f64(b);
   if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute Position3D (Vec3f64) not found in PointLayout of buffer");
   return m;
 }
-PosView position_view(const pst_buffer& b, const Member* m) {
+pstk::Positions position_view(const pst_buffer& b, const Member* m) {
   if (b.len >= 0xFFFFFFFFull) throw Error(PST_ERR_UNSUPPORTED, "ransac: 2^32 - 1 points and more per call are not supported");
-  const AttrView v = attr_view(b, m);
-  return PosView{b.len == 0 ? nullptr : (const uint8_t*)(uintptr_t)v.addr, v.stride, b.len};
+  pstk::Positions p = positions_of(b, *m);
+  if (b.len == 0) p.base = nullptr;
+  return p;
 }
-
-struct Scratch {
-  pstk::DevBuf buf;
-  void* get(size_t bytes, hipStream_t s) {
-    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure("ransac: scratch allocation failed: ");
-    return buf.p;
-  }
-};
 
 struct FitResult { uint64_t best, ranking; double model[6]; };
 
 // checks shared by *_fit and the seeded entry points, in the order the header documents
-PosView fit_checks(const pst_buffer* b, size_t iterations, bool line) {
+pstk::Positions fit_checks(const pst_buffer* b, size_t iterations, bool line) {
   not_null(b, "buffer");
   if (iterations == 0)  // the reference unwraps the max_by of an empty iterator
     throw Error(PST_ERR_INVALID_ARGUMENT, "called `Option::unwrap()` on a `None` value (num_of_iterations is 0)");
@@ -76,7 +67,7 @@ PosView fit_checks(const pst_buffer* b, size_t iterations, bool line) {
   return position_view(*b, m);
 }
 
-FitResult fit(const PosView& pv, bool line, double thr, const uint64_t* samples, size_t iterations, uint64_t* rankings) {
+FitResult fit(const pstk::Positions& pv, bool line, double thr, const uint64_t* samples, size_t iterations, uint64_t* rankings) {
   const size_t per = line ? 2 : 3;
   for (size_t it = 0; it < iterations; ++it) {
     const uint64_t* s = samples + it * per;
@@ -88,18 +79,18 @@ FitResult fit(const PosView& pv, bool line, double thr, const uint64_t* samples,
   hipStream_t s = current_stream();
   const size_t rec_bytes = pstk::ransac_record_bytes(line);
   // one block of scratch: samples | records | rankings | result record
-  const size_t off_recs = (iterations * per * sizeof(uint64_t) + 255) & ~(size_t)255;
-  const size_t off_rank = off_recs + ((iterations * rec_bytes + 255) & ~(size_t)255);
-  const size_t off_out = off_rank + ((iterations * sizeof(uint64_t) + 255) & ~(size_t)255);
-  Scratch scratch;
-  uint8_t* base = (uint8_t*)scratch.get(off_out + 64, s);
-  PST_HIP_CHECK(hipMemcpyAsync(base, samples, iterations * per * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-  if (!pstk::ransac_fit(line, pv.base, pv.stride, pv.n, thr, (const uint64_t*)base, iterations, base + off_recs, (unsigned long long*)(base + off_rank),
-                        (unsigned long long*)(base + off_out), s))
-    throw hip_failure("ransac launch failed: ");
+  ScratchLayout layout;
+  const size_t off_samples = layout.add(iterations * per * sizeof(uint64_t)), off_recs = layout.add(iterations * rec_bytes);
+  const size_t off_rank = layout.add(iterations * sizeof(uint64_t)), off_out = layout.add(64);
+  Scratch scratch(layout, s, "ransac");
+  uint64_t* samples_dev = scratch.at<uint64_t>(off_samples);
+  unsigned long long* rank = scratch.at<unsigned long long>(off_rank);
+  unsigned long long* out = scratch.at<unsigned long long>(off_out);
+  PST_HIP_CHECK(hipMemcpyAsync(samples_dev, samples, iterations * per * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (!pstk::ransac_fit(line, pv, thr, samples_dev, iterations, scratch.at<void>(off_recs), rank, out, s)) throw hip_failure("ransac launch failed: ");
   FitResult r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, base + off_out, sizeof(r), hipMemcpyDeviceToHost, s));
-  if (rankings) PST_HIP_CHECK(hipMemcpyAsync(rankings, base + off_rank, iterations * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  PST_HIP_CHECK(hipMemcpyAsync(&r, out, sizeof(r), hipMemcpyDeviceToHost, s));
+  if (rankings) PST_HIP_CHECK(hipMemcpyAsync(rankings, rank, iterations * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   stream_sync(s);
   return r;
 }
@@ -110,7 +101,7 @@ int fit_entry(const pst_buffer* b, bool line, double thr, const uint64_t* sample
   not_null(samples, "samples");
   not_null(model, line ? "line" : "plane");
   not_null(ranking, "ranking");
-  const PosView pv = fit_checks(b, iterations, line);
+  const pstk::Positions pv = fit_checks(b, iterations, line);
   const FitResult r = fit(pv, line, thr, samples, iterations, rankings);
   std::memcpy(model, r.model, (line ? 6 : 4) * sizeof(double));
   *ranking = r.ranking;
@@ -122,7 +113,7 @@ int seeded_entry(const pst_buffer* b, bool line, double thr, size_t iterations, 
   PST_API_BEGIN
   not_null(model, line ? "line" : "plane");
   not_null(ranking, "ranking");
-  const PosView pv = fit_checks(b, iterations, line);
+  const pstk::Positions pv = fit_checks(b, iterations, line);
   const size_t per = line ? 2 : 3;
   std::vector<uint64_t> samples(iterations * per);
   sample_indices(seed, pv.n, iterations, (uint32_t)per, samples.data());
@@ -140,10 +131,10 @@ int mask_entry(const pst_buffer* b, bool line, const double* model, double thr, 
   if (b->len == 0) return PST_OK;
   not_null(device_mask, "device_mask");
   ensure_device();
-  const PosView pv = position_view(*b, m);
+  const pstk::Positions pv = position_view(*b, m);
   hipStream_t s = current_stream();
   Scratch rec;  // released in stream order behind the mask kernel
-  if (!pstk::ransac_mask(line, pv.base, pv.stride, pv.n, model, thr, rec.get(pstk::ransac_record_bytes(line), s), device_mask, s))
+  if (!pstk::ransac_mask(line, pv, model, thr, rec.alloc(pstk::ransac_record_bytes(line), s, "ransac"), device_mask, s))
     throw hip_failure("ransac mask launch failed: ");
   PST_API_END
 }
@@ -157,24 +148,23 @@ int inliers_entry(const pst_buffer* b, bool line, const double* model, double th
   *count = 0;
   if (b->len == 0) return PST_OK;
   ensure_device();
-  const PosView pv = position_view(*b, m);
+  const pstk::Positions pv = position_view(*b, m);
   hipStream_t s = current_stream();
   const size_t blocks = (pv.n + pstk::kRansacPointsPerBlock - 1) / pstk::kRansacPointsPerBlock;
   // counts[blocks + 1] (the last one zero, so that the scan's last offset is the total) | offsets[blocks + 1] | record | scan scratch
   size_t scan_bytes = 0;
   if (pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, blocks + 1, s) != hipSuccess) throw hip_failure("ransac: scan sizing failed: ");
-  const size_t off_offsets = ((blocks + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
-  const size_t off_rec = off_offsets + (((blocks + 1) * sizeof(uint64_t) + 255) & ~(size_t)255);
-  const size_t off_scan = off_rec + 256;
-  Scratch scratch;
-  uint8_t* base = (uint8_t*)scratch.get(off_scan + scan_bytes, s);
-  uint32_t* counts = (uint32_t*)base;
-  unsigned long long* offsets = (unsigned long long*)(base + off_offsets);
+  ScratchLayout layout;
+  const size_t off_counts = layout.add((blocks + 1) * sizeof(uint32_t)), off_offsets = layout.add((blocks + 1) * sizeof(uint64_t));
+  const size_t off_rec = layout.add(256), off_scan = layout.add(scan_bytes);
+  Scratch scratch(layout, s, "ransac");
+  uint32_t* counts = scratch.at<uint32_t>(off_counts);
+  unsigned long long* offsets = scratch.at<unsigned long long>(off_offsets);
+  void* rec = scratch.at<void>(off_rec);
   PST_HIP_CHECK(hipMemsetAsync(counts + blocks, 0, sizeof(uint32_t), s));
-  if (!pstk::ransac_model_record(line, model, thr, base + off_rec, s) ||
-      !pstk::ransac_index_pass(line, pv.base, pv.stride, pv.n, base + off_rec, counts, offsets, nullptr, false, s))
+  if (!pstk::ransac_model_record(line, model, thr, rec, s) || !pstk::ransac_index_pass(line, pv, rec, counts, offsets, nullptr, false, s))
     throw hip_failure("ransac inlier count launch failed: ");
-  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(base + off_scan, scan_bytes, counts, offsets, blocks + 1, s));
+  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(scratch.at<void>(off_scan), scan_bytes, counts, offsets, blocks + 1, s));
   unsigned long long total = 0;
   PST_HIP_CHECK(hipMemcpyAsync(&total, offsets + blocks, sizeof(total), hipMemcpyDeviceToHost, s));
   stream_sync(s);
@@ -184,9 +174,8 @@ int inliers_entry(const pst_buffer* b, bool line, const double* model, double th
     throw Error(PST_ERR_RANGE, "ransac: " + std::to_string(total) + " inliers do not fit the index array of " + std::to_string(capacity));
   if (total == 0) return PST_OK;
   Scratch out;
-  unsigned long long* idx_dev = (unsigned long long*)out.get((size_t)total * sizeof(uint64_t), s);
-  if (!pstk::ransac_index_pass(line, pv.base, pv.stride, pv.n, base + off_rec, counts, offsets, idx_dev, true, s))
-    throw hip_failure("ransac inlier index launch failed: ");
+  unsigned long long* idx_dev = out.alloc<unsigned long long>((size_t)total * sizeof(uint64_t), s, "ransac");
+  if (!pstk::ransac_index_pass(line, pv, rec, counts, offsets, idx_dev, true, s)) throw hip_failure("ransac inlier index launch failed: ");
   PST_HIP_CHECK(hipMemcpyAsync(indices, idx_dev, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   stream_sync(s);
   PST_API_END

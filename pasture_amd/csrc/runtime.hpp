@@ -6,8 +6,10 @@
 #include <vector>
 
 #include "core.hpp"
+#include "device_sort.hpp"
 #include "kernels.hpp"
 #include "plan.h"
+#include "scratch_layout.hpp"
 
 // Device-backed point buffer.  One struct serves the three reference buffer kinds:
 //   VectorBuffer          (point_buffer.rs:659-945)   columnar = false, owns = true
@@ -94,6 +96,11 @@ inline AttrView attr_view(const pst_buffer& b, size_t slot, size_t first = 0) {
 inline AttrView attr_view(const pst_buffer& b, const Member* m, size_t first = 0) {
   return m ? attr_view(b, (size_t)(m - b.layout.members.data()), first) : AttrView{0, 0};
 }
+// the positions as the launchers take them; m: the buffer's Position3D member (position_vec3f64).  No checks: the length limits are the callers'
+inline pstk::Positions positions_of(const pst_buffer& b, const Member& m) {
+  const AttrView v = attr_view(b, &m);
+  return pstk::Positions{(const uint8_t*)(uintptr_t)v.addr, v.stride, b.len};
+}
 // view_attribute::<Vector3<f64>>(&POSITION_3D): exact name AND datatype (buffer_views.rs:301-310); null when the layout has none (each caller
 // throws the message of the panic it mirrors)
 inline const Member* position_vec3f64(const pst_buffer& b) {
@@ -101,6 +108,18 @@ inline const Member* position_vec3f64(const pst_buffer& b) {
   pos.datatype.kind = PST_VEC3F64;
   return b.layout.find(pos);
 }
+
+// A call's block of device scratch, as a rule carved by a ScratchLayout: allocated on the stream, released in stream order by the destructor
+struct Scratch {
+  pstk::DevBuf buf;
+  Scratch() = default;
+  Scratch(const ScratchLayout& layout, hipStream_t s, const char* who) { alloc(layout.total(), s, who); }
+  template <class T = void> T* alloc(size_t bytes, hipStream_t s, const char* who) {  // (a block that is one region)
+    if (buf.alloc(bytes, s) != hipSuccess) throw hip_failure(std::string(who) + ": scratch allocation failed: ");
+    return (T*)buf.p;
+  }
+  template <class T> T* at(size_t offset) { return (T*)((uint8_t*)buf.p + offset); }
+};
 
 // Plan execution: `entries` hold per-mapping descriptors with src_col/dst_col already resolved; the function splits them
 // into launches of <= PST_PLAN_MAX_ENTRIES, picks the LDS tile and the kernel body, and enqueues on `stream`.
