@@ -500,6 +500,75 @@ int pst_cluster_kernel_shape(uint32_t* points_per_block, uint32_t* tile_points);
  * switch.  Host only. */
 int pst_cluster_phase_times(double ms[3]);
 
+/* ---- Nearest neighbours between two clouds, ICP ----------------------------------------------------------------------------------------
+ * What CloudCompare's cloud-to-cloud distance, PDAL's filters.icp and PCL's CorrespondenceEstimation / IterativeClosestPoint compute (the
+ * reference has none of them): for every point of a QUERY cloud the nearest point of a different TARGET cloud, and on top of it the rigid
+ * alignment of one scan to another.  The definitions:
+ *   points:       target points are the Position3D (Vec3f64) of the target buffer; query points those of the query buffer, optionally sent
+ *                 through a rigid transform T of 12 doubles, row-major [R | t], as they are loaded:
+ *                 x' = ((r00*x + r01*y) + r02*z) + t0, y' and z' alike.
+ *   distance:     d2(q', p) = (dx*dx + dy*dy) + dz*dz, dx = p.x - q'.x (y, z alike).  Every operation here and above is a separately
+ *                 rounded f64 operation (no contraction).
+ *   match:        for a finite query, the finite target with the smallest d2 among those with d2 <= m2, m2 = max_distance * max_distance
+ *                 rounded once on the host; equal d2 goes to the lower target buffer index.  idx = that buffer index, dist = sqrt(d2).
+ *   no match:     idx = 0xFFFFFFFF and dist = +inf: a query that is not finite after the transform, no target within max_distance, an empty
+ *                 target, a target without a finite point.  Targets that are not finite are never matched.
+ *   max_distance: +inf means unbounded.  NaN, zero, negative, or a value whose square is neither a normal number nor +inf ->
+ *                 PST_ERR_INVALID_ARGUMENT.
+ * The result is a function of the two clouds, T and max_distance alone: not of the index's cell edge, not of the order in which the search
+ * visits cells, not of the storage kind.
+ *   ICP step:     the search with T_in; M = the matched source points, m = |M|, o = the grid origin of the index.
+ *                 first pass:  cq = o + sum(q' - o) / m, cp = o + sum(p - o) / m
+ *                 second pass: H = sum (q' - cq)(p - cp)^T, sum_d2 = sum d2
+ *                 Both are fixed-shape reductions in source-buffer order (blocks of a fixed number of points, a fixed tree per block, the
+ *                 block partials added in block order by one workgroup; no floating-point atomics): two calls give the same bits.
+ *                 sums[17] = {(double)m, cq[3], cp[3], H[9] row-major, sum_d2}.  dR = the proper rotation (orthonormal, determinant +1) that
+ *                 maximises trace(dR H) (Horn's unit quaternion; a rank-deficient H still gives a proper rotation), dt = cp - dR cq,
+ *                 T_out = (dR | dt) o T_in: R_out = dR R_in, t_out = dR t_in + dt.  rms = sqrt(sum_d2 / m) is the misfit of T_in, not of
+ *                 T_out.  m < 3 -> PST_ERR_TOO_FEW_POINTS.
+ *   ICP loop:     T_0 = T_init (NULL: the identity); the step is repeated and the loop stops after the step whose rms differs from the
+ *                 previous step's by at most rms_tolerance (absolute, in the cloud's units, >= 0), or after max_iterations steps (>= 1).
+ *                 It IS the step function called in a loop: the same bits.
+ * Checks: null arguments and invalid parameters (max_distance as above; a negative, NaN or infinite cell_edge; a transform entry that is
+ * not finite; max_iterations == 0; a negative or NaN rms_tolerance) are answered before a device is looked for; then
+ * PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64; then the device (none: PST_ERR_NO_DEVICE, never a CPU path); then the
+ * lengths: 2^32 - 16 points and more in either cloud -> PST_ERR_UNSUPPORTED.  Out of device memory is PST_ERR_OUT_OF_MEMORY and the next
+ * call works.  Both clouds may be interleaved or columnar, owned, sliced or external; query and target may be the same buffer.
+ * Cost: a query tests the targets of the 27 cells around its own and goes on ring by ring only while its best distance exceeds the rings
+ * searched.  A query far outside a large target walks ring after ring, up to the whole grid, unless max_distance bounds it. */
+typedef struct pst_nn_index pst_nn_index;
+/* The persistent index over `target`: a uniform grid over the finite points' AABB, their positions and buffer indices sorted by cell.  It
+ * owns device memory of its own (about 36 bytes per finite target; not the scratch pool: pst_release_scratch leaves it alone), does not
+ * keep `target` alive and does not read it after this call.  cell_edge > 0: the grid's cell edge (doubled until no axis has more than
+ * 2^21 - 1 cells); 0: chosen so that the occupied cells hold between 2 and 16 points on average.  Synchronous. */
+int pst_nn_index_create(const pst_buffer* target, double cell_edge, pst_nn_index** out);
+int pst_nn_index_destroy(pst_nn_index* index);
+/* What the index was built with (each pointer optional; host only): the grid's origin and its final cell edge, cells per axis, the number of
+ * finite targets and of occupied cells.  An index without a finite target reports zeros. */
+int pst_nn_index_grid(const pst_nn_index* index, double min_and_edge[4], uint32_t dim[3], uint64_t* n_finite, uint64_t* occupied_cells);
+/* Synchronous.  d_idx: len(query) x uint32, d_dist: len(query) x f64, both in DEVICE memory; either may be NULL, not both.  transform12:
+ * host, NULL = the query points as they are stored. */
+int pst_nearest_neighbours_device(const pst_nn_index* index, const pst_buffer* query, const double* transform12, double max_distance, uint32_t* d_idx,
+                                  double* d_dist);
+/* keep_far == 0: d_mask[i] = 1 iff d_dist[i] <= threshold; otherwise d_mask[i] = 1 iff NOT d_dist[i] <= threshold (true for an unmatched
+ * point).  Both arrays in DEVICE memory, n elements; stream-ordered, no host synchronisation: the mask is what
+ * pst_buffer_filter(..., PST_MEM_DEVICE, ...) and pst_buffer_filter_into_async take.  n == 0 is answered PST_OK on the host, before a device
+ * is looked for (as pst_cluster_mask_device does): there is nothing to compute. */
+int pst_distance_mask_device(const double* d_dist, uint64_t n, double threshold, int keep_far, uint8_t* d_mask);
+/* One ICP step (synchronous; all arrays on the host, T_out may be T_in). */
+int pst_icp_step(const pst_nn_index* index, const pst_buffer* source, const double T_in[12], double max_distance, double sums[17], double T_out[12]);
+/* The ICP loop (synchronous; every step copies its 17 sums to the host).  T_init: NULL = identity.  rms, matched, iterations (each
+ * optional): the last step's misfit and number of matched points, the number of steps run. */
+int pst_icp(const pst_nn_index* index, const pst_buffer* source, const double* T_init, double max_distance, uint32_t max_iterations, double rms_tolerance,
+            double T_out[12], double* rms, uint64_t* matched, uint32_t* iterations);
+/* The kernels' seams (each pointer optional; host only): queries one workgroup of the search kernel owns (one lane each; candidates are read
+ * from the index's sorted arrays, none are staged in LDS), threads of the one workgroup that adds the block partials of the ICP sums, source
+ * points per block partial. */
+int pst_nn_kernel_shape(uint32_t* queries_per_block, uint32_t* reduce_block, uint32_t* reduce_points_per_block);
+/* Measurement aid.  With PST_NN_TIMES=1 in the environment pst_nearest_neighbours_device brackets its two phases with stream events; this
+ * returns the calling thread's last call: ms = {query keys + sort, search}.  Zeros without the switch.  Host only. */
+int pst_nn_phase_times(double ms[2]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

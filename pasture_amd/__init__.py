@@ -13,6 +13,7 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          transform_attribute, Line, Plane, line_inlier_mask, line_inliers, plane_inlier_mask, plane_inliers, ransac_line,
                          ransac_line_fit, ransac_plane, ransac_plane_fit, ransac_sample_indices, OutlierStatistics, knn_search, knn_search_device,
                          outlier_kernel_shape, radius_outlier_mask, remove_radius_outliers, remove_statistical_outliers, statistical_outlier_mask,
-                         NO_CLUSTER, cluster_kernel_shape, cluster_mask, euclidean_clusters, extract_clusters)
+                         NO_CLUSTER, cluster_kernel_shape, cluster_mask, euclidean_clusters, extract_clusters, NO_MATCH, NearestNeighbourIndex,
+                         cloud_to_cloud_distances, distance_mask, icp, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

@@ -198,6 +198,15 @@ _PRODUCT_SIGNATURES = {
     "cluster_mask_device": [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P],
     "cluster_kernel_shape": [_U32P, _U32P],
     "cluster_phase_times": [_D3],
+    "nn_index_create": [_P, C.c_double, _PP],
+    "nn_index_destroy": [_P],
+    "nn_index_grid": [_P, _D3, _U32P, _U64P, _U64P],
+    "nearest_neighbours_device": [_P, _P, _D3, C.c_double, _P, _P],
+    "distance_mask_device": [_P, C.c_uint64, C.c_double, C.c_int, _P],
+    "icp_step": [_P, _P, _D3, C.c_double, _D3, _D3],
+    "icp": [_P, _P, _D3, C.c_double, C.c_uint32, C.c_double, _D3, _D3, _U64P, _U32P],
+    "nn_kernel_shape": [_U32P, _U32P, _U32P],
+    "nn_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

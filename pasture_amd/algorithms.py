@@ -488,3 +488,131 @@ def cluster_phase_times(api=None):
     ms = (C.c_double * 3)()
     (api or product_api()).cluster_phase_times(ms)
     return tuple(ms)
+
+
+# ---- nearest neighbours between two clouds, ICP (include/pasture_amd.h) ----------------------------------------------------------------------
+
+NO_MATCH = 0xFFFFFFFF
+
+
+def _transform12(transform):
+    """A 3 x 4 [R | t] (or a 4 x 4 whose last row is 0 0 0 1) as 12 C doubles, row-major; None stays None."""
+    if transform is None:
+        return None
+    t = np.asarray(transform, dtype=np.float64)
+    if t.shape == (4, 4):
+        if not np.array_equal(t[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("the last row of a 4 x 4 transform must be 0 0 0 1")
+        t = t[:3]
+    if t.shape != (3, 4):
+        raise ValueError("a transform is a 3 x 4 or 4 x 4 array")
+    return (C.c_double * 12)(*t.reshape(12))
+
+
+class NearestNeighbourIndex:
+    """The persistent nearest-neighbour index over `target` (pst_nn_index_create): a uniform grid over its finite points, kept in device memory
+    of its own until destroy().  cell_edge = 0 chooses the edge from the cloud; the target buffer is not read after construction."""
+
+    def __init__(self, target: _Buffer, cell_edge: float = 0.0):
+        self.api = target.api
+        self._h = None
+        h = C.c_void_p()
+        self.api.nn_index_create(target._h, cell_edge, C.byref(h))
+        self._h = h
+
+    def grid(self) -> dict:
+        """origin (3,), the final cell edge, cells per axis (3,), the number of finite targets and of occupied cells."""
+        me, dim, nf, occ = (C.c_double * 4)(), (C.c_uint32 * 3)(), C.c_uint64(), C.c_uint64()
+        self.api.nn_index_grid(self._h, me, dim, C.byref(nf), C.byref(occ))
+        return {"origin": tuple(me[0:3]), "cell_edge": me[3], "dim": tuple(dim), "n_finite": nf.value, "occupied_cells": occ.value}
+
+    def destroy(self) -> None:
+        if self._h is not None and self._h.value:
+            self.api.nn_index_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class _IndexFor:
+    """`target_or_index` as an index: one that is passed in stays the caller's, one built here is destroyed on exit."""
+
+    def __init__(self, target_or_index):
+        self.own = not isinstance(target_or_index, NearestNeighbourIndex)
+        self.index = NearestNeighbourIndex(target_or_index) if self.own else target_or_index
+
+    def __enter__(self):
+        return self.index
+
+    def __exit__(self, *exc):
+        if self.own:
+            self.index.destroy()
+
+
+def nearest_neighbours_device(query: _Buffer, index: NearestNeighbourIndex, max_distance: float = float("inf"), transform=None, idx_ptr: int = 0,
+                              dist_ptr: int = 0) -> None:
+    """For every point of `query` (sent through `transform` first, if given) the nearest finite target of `index` within max_distance, in
+    caller-owned DEVICE memory (addresses; 0 = not wanted, not both): buffer indices uint32 [n] (NO_MATCH without one), distances f64 [n] (+inf)."""
+    query.api.nearest_neighbours_device(index._h, query._h, _transform12(transform), max_distance, C.c_void_p(idx_ptr or None), C.c_void_p(dist_ptr or None))
+
+
+def nearest_neighbours(query: _Buffer, target_or_index, max_distance: float = float("inf"), transform=None):
+    """(idx uint32 (n,), dist float64 (n,)) as numpy arrays: the exact nearest neighbour of every query point in another cloud (a buffer, or a
+    NearestNeighbourIndex built over it once and searched many times)."""
+    from .layout import PointAttributeDataType as T
+    n = query.len()
+    idx, dist = _DeviceArray(query.api, T.U32, n), _DeviceArray(query.api, T.F64, n)
+    with _IndexFor(target_or_index) as index:
+        query.api.nearest_neighbours_device(index._h, query._h, _transform12(transform), max_distance, C.c_void_p(idx.ptr or 1), C.c_void_p(dist.ptr or 1))
+    return idx.to_numpy(), dist.to_numpy()
+
+
+def cloud_to_cloud_distances(query: _Buffer, target, max_distance: float = float("inf")) -> np.ndarray:
+    """CloudCompare's C2C distance: per query point the distance to the nearest point of `target` (a buffer or an index), +inf beyond max_distance."""
+    return nearest_neighbours(query, target, max_distance)[1]
+
+
+def distance_mask(device_dist_ptr: int, n: int, threshold: float, keep_far: bool, device_mask_ptr: int, api=None) -> None:
+    """Stream-ordered: mask[i] = 1 iff dist[i] <= threshold (keep_far: iff NOT dist[i] <= threshold, which holds for unmatched points), both arrays
+    (n f64 / n bytes) in DEVICE memory -- the mask filter / filter_into take as (device_mask_ptr, 'device')."""
+    from ._capi import product_api
+    (api or product_api()).distance_mask_device(C.c_void_p(int(device_dist_ptr) or None), n, threshold, 1 if keep_far else 0, C.c_void_p(int(device_mask_ptr) or None))
+
+
+def icp_step(index: NearestNeighbourIndex, source: _Buffer, transform, max_distance: float):
+    """One point-to-point ICP step from `transform`: (sums (17,) = [m, cq xyz, cp xyz, H row-major, sum_d2], transform_out 3 x 4).
+    sqrt(sums[16] / sums[0]) is the rms misfit of `transform`, not of transform_out."""
+    sums, out = (C.c_double * 17)(), (C.c_double * 12)()
+    source.api.icp_step(index._h, source._h, _transform12(transform), max_distance, sums, out)
+    return np.array(sums, dtype=np.float64), np.array(out, dtype=np.float64).reshape(3, 4)
+
+
+def icp(source: _Buffer, target_or_index, max_distance: float, max_iterations: int = 50, rms_tolerance: float = 0.0, init=None):
+    """Point-to-point ICP of `source` onto a target (PDAL's filters.icp, PCL's IterativeClosestPoint): (transform 3 x 4, rms, matched, iterations).
+    Stops after the step whose rms differs from the previous one's by at most rms_tolerance, or after max_iterations steps."""
+    out, rms, matched, steps = (C.c_double * 12)(), C.c_double(), C.c_uint64(), C.c_uint32()
+    with _IndexFor(target_or_index) as index:
+        source.api.icp(index._h, source._h, _transform12(init), max_distance, max_iterations, rms_tolerance, out, C.byref(rms), C.byref(matched), C.byref(steps))
+    return np.array(out, dtype=np.float64).reshape(3, 4), rms.value, matched.value, steps.value
+
+
+def nn_kernel_shape(api=None) -> dict:
+    """The seams of the nearest-neighbour kernels: queries one workgroup of the search owns, threads of the workgroup that adds the block partials
+    of the ICP sums, source points per block partial."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).nn_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("queries_per_block", "reduce_block", "reduce_points_per_block"), (x.value for x in v)))
+
+
+def nn_phase_times(api=None):
+    """(query keys + sort, search) in milliseconds of this thread's last nearest_neighbours* call; zeros unless PST_NN_TIMES=1 was set when the
+    library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 2)()
+    (api or product_api()).nn_phase_times(ms)
+    return tuple(ms)

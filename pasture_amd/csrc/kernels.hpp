@@ -239,4 +239,32 @@ bool cluster_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, u
                     uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, hipStream_t stream);
 bool cluster_mask(const uint32_t* labels, uint64_t n, uint32_t first_cluster, uint32_t cluster_count, uint8_t* mask, hipStream_t stream);
 
+// Nearest neighbours between two clouds and the sums of an ICP step (nn.hip; the index and the ICP loop are in nn_api.cpp).  The seams
+// (pst_nn_kernel_shape):
+constexpr uint32_t kNnQueriesPerBlock = 256;  // queries one workgroup of the search kernel owns, one lane each; candidates are not staged in LDS
+constexpr uint32_t kNnReduceBlock = 256;      // threads of the one workgroup that adds the block partials of the ICP sums
+constexpr uint32_t kNnReducePoints = 1024;    // source points per block partial
+// the cluster grid with the far corner of the AABB (queries are clamped into it) and the edge the ring bound is computed with
+struct NnGrid { double min[3], max[3]; double edge, edge_stop; uint32_t dim[3]; uint32_t bits[3]; };
+// x' = ((m[0]*x + m[1]*y) + m[2]*z) + m[3], ...; on == 0: the point as it is stored
+struct NnTransform { double m[12]; int on; };
+// the device-side record of one ICP step
+struct NnSums { unsigned long long matched; double cq[3], cp[3], H[9], sum_d2; };
+// positions of the nf finite points `order` names, in that order
+bool nn_gather(const Positions& pos, const uint32_t* order, uint32_t nf, double* xs, double* ys, double* zs, hipStream_t stream);
+// *count = number of different keys among sorted_keys[0, nf)
+bool nn_count_cells(const unsigned long long* sorted_keys, uint32_t nf, unsigned long long* count, hipStream_t stream);
+// keys[i] = cell key of the transformed query i clamped into the grid's AABB (all ones: not finite), vals[i] = i
+bool nn_query_keys(const Positions& pos, const NnTransform& t, const NnGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
+// query_keys / query_order: the sorted pairs (null, or nf == 0: nothing is searched and every query is unmatched).  Per query, each optional:
+// the match's target buffer index, its distance, its position in the index's sorted arrays (0xFFFFFFFF / +inf / 0xFFFFFFFF without a match)
+bool nn_search(const Positions& pos, const NnTransform& t, const NnGrid& g, double m2, const unsigned long long* query_keys, const uint32_t* query_order,
+               const unsigned long long* keys, const double* xs, const double* ys, const double* zs, const uint32_t* target_index, uint32_t nf, uint32_t* out_idx,
+               double* out_dist, uint32_t* out_at, hipStream_t stream);
+bool nn_distance_mask(const double* dist, uint64_t n, double threshold, int keep_far, uint8_t* mask, hipStream_t stream);
+size_t nn_icp_partials_bytes(uint64_t n);
+// at: what nn_search wrote as out_at for these source points and this transform
+bool nn_icp_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double origin[3],
+                 void* partials, NnSums* rec, hipStream_t stream);
+
 }  // namespace pstk
