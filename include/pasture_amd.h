@@ -529,6 +529,32 @@ int pst_cluster_phase_times(double ms[3]);
  *   ICP loop:     T_0 = T_init (NULL: the identity); the step is repeated and the loop stops after the step whose rms differs from the
  *                 previous step's by at most rms_tolerance (absolute, in the cloud's units, >= 0), or after max_iterations steps (>= 1).
  *                 It IS the step function called in a loop: the same bits.
+ *   normals:      point-to-plane ICP needs a normal per target.  pst_nn_index_set_normals* gathers the normals of the finite targets into
+ *                 the index's sorted order, as f64, in a second block of device memory the index owns (24 bytes per finite target).  They
+ *                 are used AS GIVEN, neither normalised nor re-oriented: the sign of a normal does not change the step (j and r below both
+ *                 change sign, every sum is bit-identical), and a normal that is not of unit length weights its pair by its squared
+ *                 length, as in PCL.
+ *   plane step:   the search with T_in exactly as in the ICP step; M the matched source points, m = |M|.  A matched pair (q', p, n), n
+ *                 the normal of p, is USED when n's three components are finite and (nx*nx + ny*ny) + nz*nz > 0; U = the used pairs,
+ *                 u = |U|, o = the grid origin.
+ *                 first pass, over U:  cq = o + sum(q' - o) / u, sum_d2 = sum d2, and the counts m and u
+ *                 second pass, over U: w = q' - cq;  a = w x n: a0 = w1*n2 - w2*n1, a1 = w2*n0 - w0*n2, a2 = w0*n1 - w1*n0;
+ *                                      r = ((p0 - q'0)*n0 + (p1 - q'1)*n1) + (p2 - q'2)*n2;  j = (a0, a1, a2, n0, n1, n2);
+ *                                      A[i][k] = sum j_i*j_k (i <= k), g_i = sum j_i*r, sum_r2 = sum r*r,
+ *                                      sum_w2 = sum ((w0*w0 + w1*w1) + w2*w2)
+ *                 Every operation is a separately rounded f64 operation; both passes are fixed-shape reductions of the form above (the same
+ *                 constants, pst_nn_kernel_shape): two calls give the same bits.
+ *                 sums[35] = {(double)m, (double)u, cq[3], A[21] (upper triangle, row-major), g[6], sum_r2, sum_w2, sum_d2}.
+ *                 The update minimises sum (r - omega.a - tau.n)^2 over a rotation vector omega about cq and a translation tau.  With
+ *                 L = sqrt(sum_w2 / u) (1 when that is 0 or not finite), S = diag(1/L, 1/L, 1/L, 1, 1, 1), A' = S A S, g' = S g and the
+ *                 eigen-decomposition A' = sum lambda_i v_i v_i^T (cyclic Jacobi): y = sum over lambda_i > 2^-30 * lambda_max of
+ *                 v_i (v_i . g') / lambda_i, the minimum-norm solution -- a direction the pairs do not constrain (all normals parallel: three
+ *                 of them; a sphere: the rotations; a cylinder: one rotation and one translation) gets NO motion.  2^-30 is a definition.
+ *                 lambda_max <= 0 or a non-finite A gives the identity update.  omega = y[0..3] / L, tau = y[3..6], dR = exp([omega]x)
+ *                 (Rodrigues; a proper rotation to rounding for any omega), dt = (cq + tau) - dR cq, T_out = (dR | dt) o T_in.
+ *                 rms = sqrt(sum_r2 / u) is the point-to-plane misfit of T_in, not of T_out.  u < 6 -> PST_ERR_TOO_FEW_POINTS; an index
+ *                 without normals -> PST_ERR_MISSING_ATTRIBUTE, after the argument checks and before a device is looked for.
+ *   plane loop:   pst_icp_plane is pst_icp_plane_step in a loop with the stopping rule of the ICP loop on that rms: the same bits.
  * Checks: null arguments and invalid parameters (max_distance as above; a negative, NaN or infinite cell_edge; a transform entry that is
  * not finite; max_iterations == 0; a negative or NaN rms_tolerance) are answered before a device is looked for; then
  * PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64; then the device (none: PST_ERR_NO_DEVICE, never a CPU path); then the
@@ -561,6 +587,27 @@ int pst_icp_step(const pst_nn_index* index, const pst_buffer* source, const doub
  * optional): the last step's misfit and number of matched points, the number of steps run. */
 int pst_icp(const pst_nn_index* index, const pst_buffer* source, const double* T_init, double max_distance, uint32_t max_iterations, double rms_tolerance,
             double T_out[12], double* rms, uint64_t* matched, uint32_t* iterations);
+/* Target normals for point-to-plane ICP; both setters are synchronous, replace what an earlier set left, and do not read their source after
+ * they return.  The normals live in device memory of the index's own (24 bytes per finite target; not the scratch pool: pst_release_scratch
+ * leaves it alone), freed by pst_nn_index_destroy.  They are used as given: not normalised (a non-unit normal weights its pair), not
+ * re-oriented (the sign of a normal does not change the step).  An index without a finite target accepts normals and holds none.
+ * Checks: null arguments, then a wrong n / len(b) (PST_ERR_INVALID_ARGUMENT), then a buffer without a Vec3f32 Normal
+ * (PST_ERR_MISSING_ATTRIBUTE), all before a device is looked for; then the device.
+ * d_normals: DEVICE memory, f64 [n][3] in target-buffer order: what pst_compute_normals_device writes.  n must equal the target's length at
+ * pst_nn_index_create.  NULL (n ignored) drops the normals (host only). */
+int pst_nn_index_set_normals_device(pst_nn_index* index, const double* d_normals, uint64_t n);
+/* The NORMAL attribute (Vec3f32) of `b` -- what pst_compute_normals_into writes -- widened to f64 (exact); b interleaved or columnar, owned, sliced
+ * or external, len(b) == the target's length. */
+int pst_nn_index_set_normals(pst_nn_index* index, const pst_buffer* b);
+/* *out = 1 when a set of normals has been accepted and not dropped since, else 0.  Host only. */
+int pst_nn_index_has_normals(const pst_nn_index* index, int* out);
+/* One point-to-plane ICP step (synchronous; all arrays on the host, T_out may be T_in).  Argument checks, limits, out-of-memory behaviour
+ * and storages are those of pst_icp_step. */
+int pst_icp_plane_step(const pst_nn_index* index, const pst_buffer* source, const double T_in[12], double max_distance, double sums[35], double T_out[12]);
+/* The point-to-plane loop (synchronous; every step copies its 35 sums to the host), as pst_icp.  rms, used, iterations (each optional): the last
+ * step's point-to-plane misfit and number of used pairs, the number of steps run. */
+int pst_icp_plane(const pst_nn_index* index, const pst_buffer* source, const double* T_init, double max_distance, uint32_t max_iterations, double rms_tolerance,
+                  double T_out[12], double* rms, uint64_t* used, uint32_t* iterations);
 /* The kernels' seams (each pointer optional; host only): queries one workgroup of the search kernel owns (one lane each; candidates are read
  * from the index's sorted arrays, none are staged in LDS), threads of the one workgroup that adds the block partials of the ICP sums, source
  * points per block partial. */

@@ -205,6 +205,11 @@ _PRODUCT_SIGNATURES = {
     "distance_mask_device": [_P, C.c_uint64, C.c_double, C.c_int, _P],
     "icp_step": [_P, _P, _D3, C.c_double, _D3, _D3],
     "icp": [_P, _P, _D3, C.c_double, C.c_uint32, C.c_double, _D3, _D3, _U64P, _U32P],
+    "nn_index_set_normals_device": [_P, _P, C.c_uint64],
+    "nn_index_set_normals": [_P, _P],
+    "nn_index_has_normals": [_P, C.POINTER(C.c_int)],
+    "icp_plane_step": [_P, _P, _D3, C.c_double, _D3, _D3],
+    "icp_plane": [_P, _P, _D3, C.c_double, C.c_uint32, C.c_double, _D3, _D3, _U64P, _U32P],
     "nn_kernel_shape": [_U32P, _U32P, _U32P],
     "nn_phase_times": [_D3],
 }

@@ -526,6 +526,42 @@ class NearestNeighbourIndex:
         self.api.nn_index_grid(self._h, me, dim, C.byref(nf), C.byref(occ))
         return {"origin": tuple(me[0:3]), "cell_edge": me[3], "dim": tuple(dim), "n_finite": nf.value, "occupied_cells": occ.value}
 
+    def set_normals(self, normals, n: Optional[int] = None) -> None:
+        """The target's normals for icp_plane, kept in the index (in device memory of its own) and used as given: not normalised, not
+        re-oriented.  `normals` is a buffer of the target's length with a NORMAL attribute (what compute_normals_into fills), or the address
+        of f64 [n][3] in DEVICE memory in target-buffer order with its length `n` (what compute_normals_device writes), or None, which drops
+        them.  Synchronous: the source is not read after the call; a later call replaces the normals."""
+        if normals is None:
+            self.api.nn_index_set_normals_device(self._h, None, 0)
+        elif isinstance(normals, (int, np.integer)):
+            if n is None or not normals:
+                raise ValueError("a device address must not be 0 and needs the number of normals, n")
+            self.api.nn_index_set_normals_device(self._h, C.c_void_p(int(normals)), n)
+        else:
+            self.api.nn_index_set_normals(self._h, normals._h)
+
+    @property
+    def has_normals(self) -> bool:
+        out = C.c_int()
+        self.api.nn_index_has_normals(self._h, C.byref(out))
+        return bool(out.value)
+
+    @classmethod
+    def with_normals(cls, target: _Buffer, k_nn: int = 16, cell_edge: float = 0.0) -> "NearestNeighbourIndex":
+        """The index over `target` with the normals compute_normals_device estimates from k_nn neighbours (their signs are arbitrary, which
+        point-to-plane ICP does not mind); the temporary device array of the normals is released before this returns."""
+        from .layout import PointAttributeDataType as T
+        index = cls(target, cell_edge)
+        try:
+            n = target.len()
+            normals = _DeviceArray(target.api, T.F64, 3 * n)
+            compute_normals_device(target, k_nn, normals_ptr=normals.ptr)
+            index.set_normals(normals.ptr, n)
+        except Exception:
+            index.destroy()
+            raise
+        return index
+
     def destroy(self) -> None:
         if self._h is not None and self._h.value:
             self.api.nn_index_destroy(self._h)
@@ -598,6 +634,27 @@ def icp(source: _Buffer, target_or_index, max_distance: float, max_iterations: i
     with _IndexFor(target_or_index) as index:
         source.api.icp(index._h, source._h, _transform12(init), max_distance, max_iterations, rms_tolerance, out, C.byref(rms), C.byref(matched), C.byref(steps))
     return np.array(out, dtype=np.float64).reshape(3, 4), rms.value, matched.value, steps.value
+
+
+def icp_plane_step(index: NearestNeighbourIndex, source: _Buffer, transform, max_distance: float):
+    """One point-to-plane ICP step from `transform` on an index that has normals: (sums (35,) = [m, u, cq xyz, A (21: upper triangle of the
+    6 x 6, row-major), g (6), sum_r2, sum_w2, sum_d2], transform_out 3 x 4).  sqrt(sums[32] / sums[1]) is the point-to-plane rms misfit of
+    `transform`, not of transform_out."""
+    sums, out = (C.c_double * 35)(), (C.c_double * 12)()
+    source.api.icp_plane_step(index._h, source._h, _transform12(transform), max_distance, sums, out)
+    return np.array(sums, dtype=np.float64), np.array(out, dtype=np.float64).reshape(3, 4)
+
+
+def icp_plane(source: _Buffer, index: NearestNeighbourIndex, max_distance: float, max_iterations: int = 50, rms_tolerance: float = 0.0, init=None):
+    """Point-to-plane ICP of `source` onto the target of `index` (PCL's IterativeClosestPointWithNormals, Open3D's
+    TransformationEstimationPointToPlane): (transform 3 x 4, rms, used pairs, iterations), with the stopping rule of icp on the point-to-plane
+    rms.  `index` must be a NearestNeighbourIndex that has normals (set_normals, or NearestNeighbourIndex.with_normals): a buffer in its place
+    is refused with a TypeError, because how its normals are to be estimated (k_nn) is the caller's choice, not a default of the loop."""
+    if not isinstance(index, NearestNeighbourIndex):
+        raise TypeError("icp_plane needs a NearestNeighbourIndex with normals (NearestNeighbourIndex.with_normals(target, k_nn)), not a buffer")
+    out, rms, used, steps = (C.c_double * 12)(), C.c_double(), C.c_uint64(), C.c_uint32()
+    source.api.icp_plane(index._h, source._h, _transform12(init), max_distance, max_iterations, rms_tolerance, out, C.byref(rms), C.byref(used), C.byref(steps))
+    return np.array(out, dtype=np.float64).reshape(3, 4), rms.value, used.value, steps.value
 
 
 def nn_kernel_shape(api=None) -> dict:

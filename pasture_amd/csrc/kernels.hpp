@@ -266,5 +266,13 @@ size_t nn_icp_partials_bytes(uint64_t n);
 // at: what nn_search wrote as out_at for these source points and this transform
 bool nn_icp_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double origin[3],
                  void* partials, NnSums* rec, hipStream_t stream);
+// Point-to-plane: the target normals in the index's sorted order, and the sums of a point-to-plane step.
+// the device-side record of one point-to-plane step: A the upper triangle of sum j j^T row-major, j = ((q' - cq) x n, n); g = sum j r
+struct NnPlaneSums { unsigned long long matched, used; double cq[3], A[21], g[6], sum_r2, sum_w2, sum_d2; };
+// nx[s], ny[s], nz[s] = the normal of target order[s], widened to f64: three f64 (is_f32 == false) or three f32 at base + order[s] * stride
+bool nn_gather_normals(const uint8_t* base, uint64_t stride, bool is_f32, const uint32_t* order, uint32_t nf, double* nx, double* ny, double* nz, hipStream_t stream);
+size_t nn_plane_partials_bytes(uint64_t n);
+bool nn_plane_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double* nx,
+                   const double* ny, const double* nz, const double origin[3], void* partials, NnPlaneSums* rec, hipStream_t stream);
 
 }  // namespace pstk

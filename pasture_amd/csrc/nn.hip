@@ -41,6 +41,10 @@
 // adds its four points (stride kBlock) in order, the wave folds in a fixed xor tree, the four waves' sums are added in wave order; ONE
 // workgroup then adds the block partials, thread t the contiguous run [t * c, (t + 1) * c) in block order, then the same tree.  No
 // floating-point atomics: two calls give the same bits.
+//
+// The point-to-plane step (nn_plane_*_kernel) has the same two passes over the pairs whose target normal is finite and not zero: cq and
+// sum d2 first, then with w = q' - cq, a = w x n, r = (p - q') . n, j = (a, n) the 21 + 6 + 2 sums A = sum j j^T (upper triangle), g = sum j r,
+// sum r^2, sum |w|^2.  The normals are the index's, gathered into its sorted order by nn_gather_normals_kernel and used as given.
 #include "positions_device.hpp"
 
 using namespace pstd;
@@ -206,33 +210,43 @@ __global__ __launch_bounds__(kBlock) void nn_distance_mask_kernel(const double* 
 // the device-side record of one step: the first pass leaves the count and the centroids for the second one
 using Sums = pstk::NnSums;
 
-// wave: xor tree; block: the waves' sums in wave order.  The result is valid in thread 0.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], unsigned long long& c, double* sv, unsigned long long* sc) {
+// wave: xor tree; block: the waves' sums in wave order.  The result is valid in thread 0.  C counters travel with the N sums (sc: C per wave).
+template <int N, int C>
+__device__ __forceinline__ void block_sum(double (&v)[N], unsigned long long (&c)[C], double* sv, unsigned long long* sc) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = v[k] + shfl_xor_any(v[k], off);
-    c = c + shfl_xor_any(c, off);
+#pragma unroll
+    for (int k = 0; k < C; ++k) c[k] = c[k] + shfl_xor_any(c[k], off);
   }
   const uint32_t wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < N; ++k) sv[wave * N + k] = v[k];
-    sc[wave] = c;
+#pragma unroll
+    for (int k = 0; k < C; ++k) sc[wave * C + k] = c[k];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = sv[k];
-    c = sc[0];
+#pragma unroll
+    for (int k = 0; k < C; ++k) c[k] = sc[k];
 #pragma unroll
     for (uint32_t w = 1; w < kBlock / 64; ++w) {
 #pragma unroll
       for (int k = 0; k < N; ++k) v[k] = v[k] + sv[w * N + k];
-      c = c + sc[w];
+#pragma unroll
+      for (int k = 0; k < C; ++k) c[k] = c[k] + sc[w * C + k];
     }
   }
+}
+template <int N>
+__device__ __forceinline__ void block_sum(double (&v)[N], unsigned long long& c, double* sv, unsigned long long* sc) {
+  unsigned long long one[1] = {c};
+  block_sum<N, 1>(v, one, sv, sc);
+  c = one[0];
 }
 
 constexpr int kTerms0 = 6, kTerms1 = 10;  // pass 0: sum (q' - o), sum (p - o); pass 1: H row-major, sum d2
@@ -320,6 +334,125 @@ __global__ __launch_bounds__(kBlock) void nn_icp_final_kernel(const double* __re
   }
 }
 
+// ---- the sums of a point-to-plane step --------------------------------------------------------------------------------------------------------
+// The normals of the finite targets in the index's sorted order, widened to f64 (exact).  T = double: the [n][3] array of
+// pst_compute_normals_device; T = float: a Vec3f32 attribute at any stride and byte offset.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void nn_gather_normals_kernel(cgptr_t base, uint64_t stride, const uint32_t* __restrict__ order, uint32_t nf, double* __restrict__ nx,
+                                                                   double* __restrict__ ny, double* __restrict__ nz) {
+  const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+  if (s >= nf) return;
+  cgptr_t q = base + (uint64_t)order[s] * stride;
+  nx[s] = (double)load_un<T>(q); ny[s] = (double)load_un<T>(q + sizeof(T)); nz[s] = (double)load_un<T>(q + 2 * sizeof(T));
+}
+
+using PlaneSums = pstk::NnPlaneSums;
+
+// pass 0: sum (q' - o), sum d2 over the used pairs; counters: matched, used.  pass 1: A (21), g (6), sum r^2, sum |w|^2 over the used pairs.
+constexpr int kPlaneTerms0 = 4, kPlaneTerms1 = 29, kPlaneCounts = 2;
+// position of A[i][k], i <= k, in the row-major upper triangle of a 6 x 6
+__host__ __device__ constexpr int tri6(int i, int k) { return i * 6 - i * (i - 1) / 2 + (k - i); }
+static_assert(tri6(0, 0) == 0 && tri6(1, 1) == 6 && tri6(5, 5) == 20, "row-major upper triangle");
+
+// a pair is used when its normal is finite and not zero
+__device__ __forceinline__ bool usable(double n0, double n1, double n2) {
+  return finite(n0) && finite(n1) && finite(n2) && (n0 * n0 + n1 * n1) + n2 * n2 > 0.0;
+}
+
+// partials: `blocks` records of N doubles, then `blocks` pairs of counts.  Every accumulator index below is a compile-time constant after
+// unrolling: the 29 sums of pass 1 stay in registers.
+template <int PASS>
+__global__ __launch_bounds__(kBlock) void nn_plane_partial_kernel(Pos pos, uint64_t n, Xform t, const uint32_t* __restrict__ at, const double* __restrict__ xs,
+                                                                  const double* __restrict__ ys, const double* __restrict__ zs, const double* __restrict__ nx,
+                                                                  const double* __restrict__ ny, const double* __restrict__ nz, double ox, double oy, double oz,
+                                                                  const PlaneSums* __restrict__ rec, double* __restrict__ psum, unsigned long long* __restrict__ pcount) {
+  constexpr int N = PASS == 0 ? kPlaneTerms0 : kPlaneTerms1;
+  __shared__ double sv[(kBlock / 64) * N];
+  __shared__ unsigned long long sc[(kBlock / 64) * kPlaneCounts];
+  double cq0 = 0.0, cq1 = 0.0, cq2 = 0.0;
+  if constexpr (PASS == 1) { cq0 = rec->cq[0]; cq1 = rec->cq[1]; cq2 = rec->cq[2]; }
+  const uint64_t first = (uint64_t)blockIdx.x * kRP;
+  double v[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = 0.0;
+  unsigned long long c[kPlaneCounts] = {0, 0};
+#pragma unroll 1
+  for (uint32_t j = 0; j < kRP / kBlock; ++j) {
+    const uint64_t i = first + j * kBlock + threadIdx.x;
+    if (i >= n) continue;
+    const uint32_t a = at[i];
+    if (a == kNone) continue;
+    c[0] += 1;
+    const double n0 = nx[a], n1 = ny[a], n2 = nz[a];
+    if (!usable(n0, n1, n2)) continue;
+    c[1] += 1;
+    double qx, qy, qz;
+    load_point(pos, i, qx, qy, qz);
+    apply(t, qx, qy, qz);
+    const double dx = xs[a] - qx, dy = ys[a] - qy, dz = zs[a] - qz;
+    if constexpr (PASS == 0) {
+      v[0] = v[0] + (qx - ox); v[1] = v[1] + (qy - oy); v[2] = v[2] + (qz - oz);
+      v[3] = v[3] + ((dx * dx + dy * dy) + dz * dz);
+    } else {
+      const double w0 = qx - cq0, w1 = qy - cq1, w2 = qz - cq2;
+      const double jv[6] = {w1 * n2 - w2 * n1, w2 * n0 - w0 * n2, w0 * n1 - w1 * n0, n0, n1, n2};
+      const double r = (dx * n0 + dy * n1) + dz * n2;
+#pragma unroll
+      for (int p = 0; p < 6; ++p) {
+#pragma unroll
+        for (int q = p; q < 6; ++q) v[tri6(p, q)] = v[tri6(p, q)] + jv[p] * jv[q];
+        v[21 + p] = v[21 + p] + jv[p] * r;
+      }
+      v[27] = v[27] + r * r;
+      v[28] = v[28] + ((w0 * w0 + w1 * w1) + w2 * w2);
+    }
+  }
+  block_sum<N, kPlaneCounts>(v, c, sv, sc);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) psum[(uint64_t)blockIdx.x * N + k] = v[k];
+    pcount[2 * (uint64_t)blockIdx.x] = c[0];
+    pcount[2 * (uint64_t)blockIdx.x + 1] = c[1];
+  }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(kBlock) void nn_plane_final_kernel(const double* __restrict__ psum, const unsigned long long* __restrict__ pcount, uint64_t blocks, double ox,
+                                                                double oy, double oz, PlaneSums* __restrict__ rec) {
+  constexpr int N = PASS == 0 ? kPlaneTerms0 : kPlaneTerms1;
+  __shared__ double sv[(kBlock / 64) * N];
+  __shared__ unsigned long long sc[(kBlock / 64) * kPlaneCounts];
+  const uint64_t per = (blocks + kRB - 1) / kRB, b0 = threadIdx.x * per, b1 = b0 + per < blocks ? b0 + per : blocks;
+  double v[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = 0.0;
+  unsigned long long c[kPlaneCounts] = {0, 0};
+  for (uint64_t b = b0; b < b1; ++b) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = v[k] + psum[b * N + k];
+    c[0] = c[0] + pcount[2 * b];
+    c[1] = c[1] + pcount[2 * b + 1];
+  }
+  block_sum<N, kPlaneCounts>(v, c, sv, sc);
+  if (threadIdx.x != 0) return;
+  if constexpr (PASS == 0) {
+    const double u = (double)c[1];
+    rec->matched = c[0];
+    rec->used = c[1];
+    rec->cq[0] = ox + v[0] / u;  // no used pair: 0 / 0, and the host answers before it reads them
+    rec->cq[1] = oy + v[1] / u;
+    rec->cq[2] = oz + v[2] / u;
+    rec->sum_d2 = v[3];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 21; ++k) rec->A[k] = v[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec->g[k] = v[21 + k];
+    rec->sum_r2 = v[27];
+    rec->sum_w2 = v[28];
+  }
+}
+
 }  // namespace
 
 namespace pstk {
@@ -368,6 +501,32 @@ bool nn_icp_sums(const Positions& pos, const NnTransform& t, const uint32_t* at,
   hipLaunchKernelGGL(nn_icp_final_kernel<0>, dim3(1), dim3(kBlock), 0, stream, (const double*)psum, (const unsigned long long*)pcount, (uint64_t)blocks, ox, oy, oz, rec);
   hipLaunchKernelGGL(nn_icp_partial_kernel<1>, dim3(blocks), dim3(kBlock), 0, stream, pos_of(pos), pos.n, t, at, xs, ys, zs, ox, oy, oz, (const NnSums*)rec, psum, pcount);
   hipLaunchKernelGGL(nn_icp_final_kernel<1>, dim3(1), dim3(kBlock), 0, stream, (const double*)psum, (const unsigned long long*)pcount, (uint64_t)blocks, ox, oy, oz, rec);
+  return launched();
+}
+
+bool nn_gather_normals(const uint8_t* base, uint64_t stride, bool is_f32, const uint32_t* order, uint32_t nf, double* nx, double* ny, double* nz, hipStream_t stream) {
+  if (nf == 0) return true;
+  if (is_f32)
+    hipLaunchKernelGGL(nn_gather_normals_kernel<float>, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, (cgptr_t)base, stride, order, nf, nx, ny, nz);
+  else
+    hipLaunchKernelGGL(nn_gather_normals_kernel<double>, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, (cgptr_t)base, stride, order, nf, nx, ny, nz);
+  return launched();
+}
+
+size_t nn_plane_partials_bytes(uint64_t n) { return (size_t)blocks_of(n, kRP) * (kPlaneTerms1 + kPlaneCounts) * 8; }
+
+bool nn_plane_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double* nx,
+                   const double* ny, const double* nz, const double origin[3], void* partials, NnPlaneSums* rec, hipStream_t stream) {
+  const unsigned blocks = blocks_of(pos.n, kRP);
+  double* psum = (double*)partials;
+  unsigned long long* pcount = (unsigned long long*)(psum + (size_t)blocks * kPlaneTerms1);
+  const double ox = origin[0], oy = origin[1], oz = origin[2];
+  hipLaunchKernelGGL(nn_plane_partial_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, pos_of(pos), pos.n, t, at, xs, ys, zs, nx, ny, nz, ox, oy, oz,
+                     (const NnPlaneSums*)rec, psum, pcount);
+  hipLaunchKernelGGL(nn_plane_final_kernel<0>, dim3(1), dim3(kBlock), 0, stream, (const double*)psum, (const unsigned long long*)pcount, (uint64_t)blocks, ox, oy, oz, rec);
+  hipLaunchKernelGGL(nn_plane_partial_kernel<1>, dim3(blocks), dim3(kBlock), 0, stream, pos_of(pos), pos.n, t, at, xs, ys, zs, nx, ny, nz, ox, oy, oz,
+                     (const NnPlaneSums*)rec, psum, pcount);
+  hipLaunchKernelGGL(nn_plane_final_kernel<1>, dim3(1), dim3(kBlock), 0, stream, (const double*)psum, (const unsigned long long*)pcount, (uint64_t)blocks, ox, oy, oz, rec);
   return launched();
 }
 

@@ -1,9 +1,11 @@
-// pst_nn_index_* / pst_nearest_neighbours_device / pst_distance_mask_device / pst_icp_step / pst_icp / pst_nn_kernel_shape: argument checks, the
-// persistent index over a target cloud, the scratch of a search and the ICP loop around nn.hip (where the definitions and the ring argument are).
+// pst_nn_index_* / pst_nearest_neighbours_device / pst_distance_mask_device / pst_icp_step / pst_icp / pst_icp_plane_step / pst_icp_plane /
+// pst_nn_kernel_shape: argument checks, the persistent index over a target cloud and its normals, the scratch of a search and the two ICP loops
+// around nn.hip (where the definitions and the ring argument are).
 #include <cmath>
 #include <cstring>
 
 #include "device_sort.hpp"
+#include "plane_solve.hpp"
 #include "rigid_solve.hpp"
 #include "runtime.hpp"
 
@@ -12,6 +14,9 @@ using namespace pst;
 // The index owns ONE block of device memory from the driver (not the stream-ordered pool, not a call's scratch: pst_release_scratch cannot
 // reach it): sorted keys | xs | ys | zs | buffer index of every sorted position, for the nf finite targets.  Nothing of the target buffer is
 // kept: the index is valid after the buffer has changed or gone.
+// Target normals (pst_nn_index_set_normals*) live in a SECOND block from the driver, nx | ny | nz in the same sorted order, 24 bytes per
+// finite target; an index over a target without a finite point accepts normals and holds none.  An all-zero pst_nn_index is an index over
+// an empty target without normals (the host-side tests stand one up that way).
 struct pst_nn_index {
   pstk::NnGrid grid{};
   uint32_t nf = 0;
@@ -20,8 +25,19 @@ struct pst_nn_index {
   uint64_t* keys = nullptr;
   double *xs = nullptr, *ys = nullptr, *zs = nullptr;
   uint32_t* order = nullptr;
+  uint64_t n_target = 0;  // the target's length at creation: what a set of normals must have
+  bool has_normals = false;
+  void* normals_block = nullptr;
+  double *nx = nullptr, *ny = nullptr, *nz = nullptr;
+  void drop_normals() {
+    if (normals_block) (void)hipFree(normals_block);
+    normals_block = nullptr;
+    nx = ny = nz = nullptr;
+    has_normals = false;
+  }
   ~pst_nn_index() {
     if (block) (void)hipFree(block);
+    if (normals_block) (void)hipFree(normals_block);
   }
 };
 
@@ -212,6 +228,68 @@ uint64_t icp_step(const pst_nn_index& ix, const pstk::Positions& pos, const doub
   return r.matched;
 }
 
+// One point-to-plane step on checked arguments (the index has normals): sums[35] and T_out; returns the number of used pairs.
+uint64_t icp_plane_step(const pst_nn_index& ix, const pstk::Positions& pos, const double T_in[12], double m2, double sums[35], double T_out[12], hipStream_t s,
+                        const char* who) {
+  pstk::NnTransform t{};
+  t.on = 1;
+  std::memcpy(t.m, T_in, sizeof(t.m));
+  pstk::NnPlaneSums r{};
+  if (pos.n && ix.nf) {  // (no finite target: no normals are held and nothing can match)
+    Search search;
+    size_t off = 0;
+    const size_t part = up256(pstk::nn_plane_partials_bytes(pos.n));
+    search.run(ix, pos, t, m2, nullptr, nullptr, true, part + 512, &off, s, who);
+    void* partials = search.scratch.at<void>(off);
+    pstk::NnPlaneSums* rec = search.scratch.at<pstk::NnPlaneSums>(off + part);
+    if (!pstk::nn_plane_sums(pos, t, search.at, ix.xs, ix.ys, ix.zs, ix.nx, ix.ny, ix.nz, ix.grid.min, partials, rec, s))
+      throw hip_failure(std::string(who) + ": reduction launch failed: ");
+    PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
+    stream_sync(s);
+  }
+  if (r.used < 6) throw Error(PST_ERR_TOO_FEW_POINTS, std::string(who) + ": fewer than 6 source points have a match within max_distance whose normal is finite and not zero");
+  sums[0] = (double)r.matched;
+  sums[1] = (double)r.used;
+  std::memcpy(sums + 2, r.cq, 3 * sizeof(double));
+  std::memcpy(sums + 5, r.A, 21 * sizeof(double));
+  std::memcpy(sums + 26, r.g, 6 * sizeof(double));
+  sums[32] = r.sum_r2;
+  sums[33] = r.sum_w2;
+  sums[34] = r.sum_d2;
+  double dR[9], dt[3];
+  plane_solve(r.A, r.g, r.sum_w2, (double)r.used, r.cq, dR, dt);
+  rigid_compose(dR, dt, T_in, T_out);
+  return r.used;
+}
+
+void require_normals(const pst_nn_index& ix, const char* who) {
+  if (!ix.has_normals) throw Error(PST_ERR_MISSING_ATTRIBUTE, std::string(who) + ": the index has no normals (pst_nn_index_set_normals, pst_nn_index_set_normals_device)");
+}
+
+// The normals at base + i * stride (f64 or f32 triples, target-buffer order) gathered into a new block that replaces the index's.
+void set_normals(pst_nn_index& ix, const uint8_t* base, uint64_t stride, bool is_f32, const char* who) {
+  if (ix.nf == 0) {  // nothing to hold
+    ix.has_normals = true;
+    return;
+  }
+  hipStream_t s = current_stream();
+  const size_t f8 = up256((size_t)ix.nf * 8);
+  void* block = nullptr;
+  PST_HIP_CHECK(dev_malloc_retry(&block, 3 * f8));
+  double *nx = (double*)block, *ny = (double*)((uint8_t*)block + f8), *nz = (double*)((uint8_t*)block + 2 * f8);
+  const bool launched = pstk::nn_gather_normals(base, stride, is_f32, ix.order, ix.nf, nx, ny, nz, s);
+  const hipError_t synced = launched ? hipStreamSynchronize(s) : hipSuccess;  // the source is not read after this call
+  if (!launched || synced != hipSuccess) {
+    (void)hipFree(block);
+    if (!launched) throw hip_failure(std::string(who) + ": gather launch failed: ");
+    PST_HIP_CHECK(synced);
+  }
+  ix.drop_normals();
+  ix.normals_block = block;
+  ix.nx = nx; ix.ny = ny; ix.nz = nz;
+  ix.has_normals = true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -242,6 +320,7 @@ int pst_nn_index_create(const pst_buffer* target, double cell_edge, pst_nn_index
   checked_length(*target, who);
   std::unique_ptr<pst_nn_index> ix(new pst_nn_index);
   const size_t n = target->len;
+  ix->n_target = n;
   if (n == 0) {  // an empty target: every query is unmatched
     *out = ix.release();
     return PST_OK;
@@ -418,6 +497,102 @@ int pst_icp(const pst_nn_index* index, const pst_buffer* source, const double* T
   std::memcpy(T_out, T, sizeof(T));
   if (rms) *rms = last_rms;
   if (matched) *matched = m;
+  if (iterations) *iterations = steps;
+  PST_API_END
+}
+
+int pst_nn_index_set_normals_device(pst_nn_index* index, const double* d_normals, uint64_t n) {
+  PST_API_BEGIN
+  const char* who = "pst_nn_index_set_normals_device";
+  not_null(index, "index");
+  if (!d_normals) {  // drop them
+    index->drop_normals();
+    return PST_OK;
+  }
+  if (n != index->n_target) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": n must equal the length the target had when the index was created");
+  ensure_device();
+  set_normals(*index, (const uint8_t*)d_normals, 24, false, who);
+  PST_API_END
+}
+
+int pst_nn_index_set_normals(pst_nn_index* index, const pst_buffer* b) {
+  PST_API_BEGIN
+  const char* who = "pst_nn_index_set_normals";
+  not_null(index, "index");
+  not_null(b, "buffer");
+  if (b->len != index->n_target) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": the buffer's length must equal the length the target had when the index was created");
+  AttributeDef nd{"Normal", DataType{}};
+  nd.datatype.kind = PST_VEC3F32;
+  const Member* nm = b->layout.find(nd);
+  if (!nm) throw Error(PST_ERR_MISSING_ATTRIBUTE, std::string(who) + ": the buffer's PointLayout has no Normal (Vec3f32)");
+  ensure_device();
+  const AttrView v = attr_view(*b, nm);
+  set_normals(*index, (const uint8_t*)(uintptr_t)v.addr, v.stride, true, who);
+  PST_API_END
+}
+
+int pst_nn_index_has_normals(const pst_nn_index* index, int* out) {
+  PST_API_BEGIN
+  not_null(index, "index");
+  not_null(out, "out");
+  *out = index->has_normals ? 1 : 0;
+  PST_API_END
+}
+
+int pst_icp_plane_step(const pst_nn_index* index, const pst_buffer* source, const double T_in[12], double max_distance, double sums[35], double T_out[12]) {
+  PST_API_BEGIN
+  const char* who = "pst_icp_plane_step";
+  not_null(index, "index");
+  not_null(source, "source");
+  not_null(T_in, "T_in");
+  not_null(sums, "sums");
+  not_null(T_out, "T_out");
+  const double m2 = checked_m2(max_distance, who);
+  const CheckedTransform t(T_in, who);
+  const Member& pm = position_member(*source);
+  require_normals(*index, who);
+  ensure_device();
+  checked_length(*source, who);
+  double out[12];
+  icp_plane_step(*index, positions_of(*source, pm), t.t.m, m2, sums, out, current_stream(), who);
+  std::memcpy(T_out, out, sizeof(out));  // (T_out may be T_in)
+  PST_API_END
+}
+
+int pst_icp_plane(const pst_nn_index* index, const pst_buffer* source, const double* T_init, double max_distance, uint32_t max_iterations, double rms_tolerance,
+                  double T_out[12], double* rms, uint64_t* used, uint32_t* iterations) {
+  PST_API_BEGIN
+  const char* who = "pst_icp_plane";
+  not_null(index, "index");
+  not_null(source, "source");
+  not_null(T_out, "T_out");
+  const double m2 = checked_m2(max_distance, who);
+  const CheckedTransform t(T_init, who);
+  if (max_iterations == 0) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": max_iterations must be at least 1");
+  if (!(rms_tolerance >= 0.0)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": rms_tolerance must not be negative");
+  const Member& pm = position_member(*source);
+  require_normals(*index, who);
+  ensure_device();
+  checked_length(*source, who);
+  const pstk::Positions pos = positions_of(*source, pm);
+  double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, next[12], sums[35];
+  if (T_init) std::memcpy(T, T_init, sizeof(T));
+  double last_rms = 0.0;
+  uint64_t u = 0;
+  uint32_t steps = 0;
+  // the stopping rule of pst_icp on the point-to-plane misfit sqrt(sum_r2 / u)
+  while (steps < max_iterations) {
+    u = icp_plane_step(*index, pos, T, m2, sums, next, current_stream(), who);
+    std::memcpy(T, next, sizeof(T));
+    const double step_rms = std::sqrt(sums[32] / sums[1]);
+    ++steps;
+    const bool settled = steps > 1 && std::fabs(step_rms - last_rms) <= rms_tolerance;
+    last_rms = step_rms;
+    if (settled) break;
+  }
+  std::memcpy(T_out, T, sizeof(T));
+  if (rms) *rms = last_rms;
+  if (used) *used = u;
   if (iterations) *iterations = steps;
   PST_API_END
 }

@@ -12,35 +12,37 @@
 
 namespace pst {
 
-// Eigen-decomposition of the symmetric 4 x 4 matrix a (destroyed: its diagonal ends as the eigenvalues); the columns of v are the eigenvectors.
-inline void jacobi_eigen4(double a[4][4], double v[4][4]) {
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+// Eigen-decomposition of the symmetric N x N matrix a (destroyed: its diagonal ends as the eigenvalues); the columns of v are the eigenvectors.
+// (N = 4: Horn's quaternion below; N = 6: the point-to-plane step of plane_solve.hpp.)
+template <int N>
+inline void jacobi_eigen(double a[N][N], double v[N][N]) {
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) v[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 64; ++sweep) {
     double off = 0.0, diag = 0.0;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < N; ++i) {
       diag += a[i][i] * a[i][i];
-      for (int j = i + 1; j < 4; ++j) off += a[i][j] * a[i][j];
+      for (int j = i + 1; j < N; ++j) off += a[i][j] * a[i][j];
     }
     if (off == 0.0 || off <= 1e-34 * diag) break;  // relative off-diagonal norm below 1e-17: nothing left at f64
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
+    for (int p = 0; p < N - 1; ++p)
+      for (int q = p + 1; q < N; ++q) {
         if (a[p][q] == 0.0) continue;
         // the rotation that annihilates a[p][q] (Golub & Van Loan, symmetric Schur decomposition): t = tan of the smaller angle
         const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
         const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
         const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {  // columns p and q
+        for (int k = 0; k < N; ++k) {  // columns p and q
           const double akp = a[k][p], akq = a[k][q];
           a[k][p] = c * akp - s * akq;
           a[k][q] = s * akp + c * akq;
         }
-        for (int k = 0; k < 4; ++k) {  // rows p and q
+        for (int k = 0; k < N; ++k) {  // rows p and q
           const double apk = a[p][k], aqk = a[q][k];
           a[p][k] = c * apk - s * aqk;
           a[q][k] = s * apk + c * aqk;
         }
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < N; ++k) {
           const double vkp = v[k][p], vkq = v[k][q];
           v[k][p] = c * vkp - s * vkq;
           v[k][q] = s * vkp + c * vkq;
@@ -48,6 +50,7 @@ inline void jacobi_eigen4(double a[4][4], double v[4][4]) {
       }
   }
 }
+inline void jacobi_eigen4(double a[4][4], double v[4][4]) { jacobi_eigen<4>(a, v); }
 
 // R (row-major, proper) maximising trace(R H), and t = cp - R cq.  H need not be finite-safe beyond this: a non-finite H gives the identity.
 inline void rigid_solve(const double H[9], const double cq[3], const double cp[3], double R[9], double t[3]) {

@@ -8,11 +8,11 @@ Two pairs of clouds of the same size, each cloud in ONE columnar Position3D buff
 Measured per pair: the index build (automatic cell edge); the search with max_distance = +inf (the sheet: only with --unbounded-on-sheet, its
 far strays among the queries each walk thousands of rings of empty cells) and with about three mean spacings, split into
 query keys + sort and search by stream events inside the call (PST_NN_TIMES=1, pst_nn_phase_times); one ICP step from the identity with the
-bounded distance; a sweep of the cell edge around the automatic one (mean points per occupied cell aimed at 1, 2, 4, 8, 16, 32; build and unbounded
+bounded distance; with --plane also the normals set in the index (pst_nn_index_set_normals_device) and one point-to-plane step; a sweep of the cell edge around the automatic one (mean points per occupied cell aimed at 1, 2, 4, 8, 16, 32; build and unbounded
 search each).  Yardsticks in the same process on the same target buffer: pst_knn_search_device with k = 3 (the nearest thing the library had:
 neighbours inside ONE cloud, index rebuilt per call) and pst_calculate_bounds (one pass over the positions).
 
-    python tools/bench_nn.py [--points 100000000] [--reps 5] [--warmup 1] [--out profiles/nn_1e8.json]
+    python tools/bench_nn.py [--points 100000000] [--reps 5] [--warmup 1] [--plane] [--out profiles/nn_1e8.json]
 """
 import argparse
 import ctypes as C
@@ -76,6 +76,20 @@ def measure(torch, alg, hip, query, target, n, spacing, args, unbounded=True):
     t_icp = timed(torch, lambda: hip.icp_step(holder["index"]._h, query._h, IDENTITY, bounded, sums, t12), args.warmup, args.reps)[0]
     out["icp_step"] = {"max_distance": bounded, "call": quartiles(t_icp), "matched": int(sums[0]), "rms": math.sqrt(sums[16] / sums[0]) if sums[0] else None}
 
+    if args.plane:
+        # point-to-plane: the normals (0, 0, 1) for every target as an f64 [n][3] device array -- what the gather and the sums cost does not
+        # depend on their values; the sheet's true normals are close to that -- set in the index, then one plane step from the identity
+        normals = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
+        normals[:, 2] = 1.0
+        t_set = timed(torch, lambda: holder["index"].set_normals(normals.data_ptr(), n), args.warmup, args.reps)[0]
+        del normals
+        sums35 = (C.c_double * 35)()
+        t_plane = timed(torch, lambda: hip.icp_plane_step(holder["index"]._h, query._h, IDENTITY, bounded, sums35, t12), args.warmup, args.reps)[0]
+        out["plane"] = {"max_distance": bounded, "set_normals": quartiles(t_set), "icp_plane_step": quartiles(t_plane), "matched": int(sums35[0]), "used": int(sums35[1]),
+                        "rms": math.sqrt(sums35[32] / sums35[1]) if sums35[1] else None}
+        holder["index"].set_normals(None)
+        say(f"  plane: set normals {out['plane']['set_normals']['median_ms']} ms, plane step {out['plane']['icp_plane_step']['median_ms']} ms")
+
     # the yardsticks, on the target buffer
     d3 = torch.empty(n * 3, dtype=torch.float64, device="cuda")
     out["knn_search_3"] = quartiles(timed(torch, lambda: hip.knn_search_device(target._h, 3, None, C.c_void_p(d3.data_ptr())), args.warmup, args.reps)[0])
@@ -118,6 +132,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--clouds", default="uniform,sheet")
     ap.add_argument("--unbounded-on-sheet", action="store_true", help="also search the sheet with max_distance = +inf: its far strays walk the whole grid")
+    ap.add_argument("--plane", action="store_true", help="also measure point-to-plane: normals set in the index and one plane step per cloud")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
