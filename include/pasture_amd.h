@@ -500,6 +500,64 @@ int pst_cluster_kernel_shape(uint32_t* points_per_block, uint32_t* tile_points);
  * switch.  Host only. */
 int pst_cluster_phase_times(double ms[3]);
 
+/* ---- Ground classification (progressive morphological filter) ------------------------------------------------------------------------
+ * What PDAL's filters.pmf and PCL's ProgressiveMorphologicalFilter compute (Zhang et al. 2003; the reference has neither), with square
+ * windows: the points are rasterised to their lowest z per cell, the raster is opened (eroded, then dilated) with growing windows, and a
+ * point is ground when it lies no higher above an opened surface than that window's threshold.  All arithmetic is f64, every operation
+ * separately rounded.  The definition:
+ *   parameters:  cell_size finite and > 0; max_window_size, slope, initial_distance, max_distance finite and >= 0; base >= 2 when
+ *                exponential != 0, >= 1 otherwise.  Anything else -> PST_ERR_INVALID_ARGUMENT.
+ *   schedule:    for k = 0, 1, ...: half-width in cells h_k = base^k (exponential) or (k + 1) * base (linear), window w_k = 2 h_k + 1;
+ *                threshold th_0 = initial_distance, th_k = min(max_distance, ((slope * (double)(w_k - w_(k-1))) * cell_size) +
+ *                initial_distance) (eq. 7 of the paper).  Window k is appended; the schedule ends after the first k with
+ *                (double)w_k * cell_size >= max_window_size.  More than 32 windows, or a half-width of 2^30 cells and more ->
+ *                PST_ERR_INVALID_ARGUMENT.
+ *   finite:      a point whose x, y and z are all finite; every other point is never ground and takes no part.
+ *   grid:        (x0, y0) = the smallest x and the smallest y of the finite points; col = (uint32)((x - x0) / cell_size), row likewise
+ *                from y; cols, rows = the largest col, row + 1.  cols * rows > 2^28 -> PST_ERR_UNSUPPORTED (use a larger cell).
+ *   surface:     Z_0[cell] = the smallest z of the cell's finite points, +inf for an empty cell.  Per window: E_k = erode(Z_k, h_k),
+ *                D_k = dilate(E_k, h_k), L = min(L, D_k + th_k) cell by cell (L starts as +inf), Z_(k+1) = D_k.
+ *                erode(A, h)[r][c] = the minimum of A over the square |dr| <= h, |dc| <= h clipped to the grid; dilate(A, h)[r][c] = the
+ *                maximum over the same square of the entries below +inf, +inf if there is none.
+ *   result:      point i is ground iff it is finite and z_i <= L[row_i][col_i].  Values are compared as values (-0.0 == 0.0).
+ * Only minima, maxima and one addition per cell and window: the result does not depend on any order of evaluation, and two calls write the
+ * same bytes.  Position3D not stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE; interleaved or columnar, owned, sliced or external, at any
+ * byte offset.  2^32 - 16 points and more -> PST_ERR_UNSUPPORTED.  Null arguments, invalid parameters and an empty buffer are answered
+ * before a device is looked for; without a device every other call is PST_ERR_NO_DEVICE, never a CPU path.
+ * Cost: the positions are read twice (raster, classification) and once more for their bounds; every window is four or more passes over a
+ * raster of 8-byte cells.  Device scratch: 32 bytes per cell. */
+/* The parameters travel as seven scalars (cell_size, max_window_size, slope, initial_distance, max_distance, exponential, base): no struct
+ * crosses the boundary.  The schedule of those parameters: *n_windows <= 32 windows, their half-widths in cells and thresholds (each array
+ * optional).  Host only. */
+int pst_pmf_schedule(double cell_size, double max_window_size, double slope, double initial_distance, double max_distance, int exponential, uint32_t base,
+                     uint32_t half_widths[32], double thresholds[32], uint32_t* n_windows);
+/* The raster's geometry, so that a caller can size the surfaces: origin = {x0, y0}, dim = {cols, rows}, *n_finite = the finite points.
+ * A buffer without a finite point (an empty one is answered on the host): zeros.  Synchronous. */
+int pst_pmf_grid(const pst_buffer* b, double cell_size, double origin[2], uint32_t dim[2], uint64_t* n_finite);
+/* Synchronous.  mask: len bytes, 1 = ground, in device memory (mask_memkind = PST_MEM_DEVICE) or host memory (anything else), the
+ * convention of the outlier masks.  surfaces (nullable; surfaces_memkind likewise): f64 [3][rows][cols] of pst_pmf_grid's dim -- the min-z
+ * raster Z_0, the last opened surface, L.  *n_ground = the ones of the mask.  An empty buffer and one without a finite point are answered
+ * without a raster: an all-zero mask, *n_ground = 0, the surfaces untouched. */
+int pst_pmf_ground_mask(const pst_buffer* b, double cell_size, double max_window_size, double slope, double initial_distance, double max_distance, int exponential, uint32_t base,
+                        uint8_t* mask, uint32_t mask_memkind, double* surfaces, uint32_t surfaces_memkind, uint64_t* n_ground);
+/* erode (op 0) / dilate (op 1) as defined above of a caller's raster, f64 [rows][cols] in DEVICE memory, by a square of half_width cells:
+ * what a terrain-model user opens or closes a surface with.  Entries are finite or +inf (a NaN counts as +inf).  Stream-ordered; NOT in
+ * place: d_in and d_out must not overlap.  cols * rows > 2^28 -> PST_ERR_UNSUPPORTED; a raster without cells is answered on the host. */
+int pst_grid_morphology_device(const double* d_in, double* d_out, uint32_t cols, uint32_t rows, uint32_t half_width, uint32_t op);
+/* d_mask[i] = 1 iff point i is finite as defined above, len bytes in DEVICE memory; stream-ordered.  With the ground mask it gives "finite
+ * and not ground", the points a ground removal keeps (pst_buffer_set_u8_where_device on the mask's own buffer clears the ground points). */
+int pst_finite_mask_device(const pst_buffer* b, uint8_t* d_mask);
+/* The U8 attribute of that name (interleaved or columnar) = value wherever the mask byte of the point, in DEVICE memory, is not zero; the
+ * other points keep theirs.  No such U8 attribute -> PST_ERR_MISSING_ATTRIBUTE.  Stream-ordered: how a ground mask becomes LAS class 2. */
+int pst_buffer_set_u8_where_device(pst_buffer* b, const char* attribute_name, const uint8_t* d_mask, uint8_t value);
+/* The kernels' seams (tests place their sizes around them; each pointer optional): points per workgroup of the raster, classification and
+ * set-where passes; columns and rows of the raster tile one workgroup of a morphology pass writes; the largest half-width of one pass (a
+ * larger one runs as successive passes whose half-widths add up to it).  Host only. */
+int pst_pmf_kernel_shape(uint32_t* points_per_block, uint32_t* tile_cols, uint32_t* tile_rows, uint32_t* max_half_width);
+/* Measurement aid.  With PST_PMF_TIMES=1 in the environment pst_pmf_ground_mask brackets its three phases with stream events; this returns
+ * the calling thread's last call: ms = {bounds + raster, morphology, classification}.  Zeros without the switch.  Host only. */
+int pst_pmf_phase_times(double ms[3]);
+
 /* ---- Nearest neighbours between two clouds, ICP ----------------------------------------------------------------------------------------
  * What CloudCompare's cloud-to-cloud distance, PDAL's filters.icp and PCL's CorrespondenceEstimation / IterativeClosestPoint compute (the
  * reference has none of them): for every point of a QUERY cloud the nearest point of a different TARGET cloud, and on top of it the rigid

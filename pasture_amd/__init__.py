@@ -14,6 +14,8 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          ransac_line_fit, ransac_plane, ransac_plane_fit, ransac_sample_indices, OutlierStatistics, knn_search, knn_search_device,
                          outlier_kernel_shape, radius_outlier_mask, remove_radius_outliers, remove_statistical_outliers, statistical_outlier_mask,
                          NO_CLUSTER, cluster_kernel_shape, cluster_mask, euclidean_clusters, extract_clusters, NO_MATCH, NearestNeighbourIndex,
-                         cloud_to_cloud_distances, distance_mask, icp, icp_plane, icp_plane_step, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape)
+                         cloud_to_cloud_distances, distance_mask, icp, icp_plane, icp_plane_step, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape,
+                         PmfParameters, classify_ground, extract_ground, grid_dilate, grid_erode, ground_mask, pmf_grid, pmf_kernel_shape, pmf_phase_times,
+                         pmf_schedule, remove_ground)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

@@ -198,6 +198,14 @@ _PRODUCT_SIGNATURES = {
     "cluster_mask_device": [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P],
     "cluster_kernel_shape": [_U32P, _U32P],
     "cluster_phase_times": [_D3],
+    "pmf_schedule": [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32, _U32P, _D3, _U32P],
+    "pmf_grid": [_P, C.c_double, _D3, _U32P, _U64P],
+    "pmf_ground_mask": [_P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _U64P],
+    "grid_morphology_device": [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32],
+    "finite_mask_device": [_P, _P],
+    "buffer_set_u8_where_device": [_P, C.c_char_p, _P, C.c_uint8],
+    "pmf_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
+    "pmf_phase_times": [_D3],
     "nn_index_create": [_P, C.c_double, _PP],
     "nn_index_destroy": [_P],
     "nn_index_grid": [_P, _D3, _U32P, _U64P, _U64P],

@@ -400,10 +400,11 @@ def radius_outlier_mask(buffer: _Buffer, radius: float, min_neighbours: int, dev
     return mask, kept.value
 
 
-def _filter_by_device_mask(buffer: _Buffer, out_buffer_type, fill):
+def _filter_by_device_mask(buffer: _Buffer, out_buffer_type, fill, whole_array: bool = False):
+    """fill(address of the mask's bytes) -- or, with whole_array, fill(the _DeviceArray that holds them) -- writes the mask and returns the call's second result"""
     from .layout import PointAttributeDataType as T
     mask = _DeviceArray(buffer.api, T.U8, buffer.len())
-    result = fill(mask.ptr)
+    result = fill(mask if whole_array else mask.ptr)
     return buffer.filter(out_buffer_type or type(buffer), (mask.ptr, "device")), result
 
 
@@ -487,6 +488,143 @@ def cluster_phase_times(api=None):
     from ._capi import product_api
     ms = (C.c_double * 3)()
     (api or product_api()).cluster_phase_times(ms)
+    return tuple(ms)
+
+
+# ---- ground classification: the progressive morphological filter (include/pasture_amd.h) -------------------------------------------------------
+
+@dataclass(frozen=True)
+class PmfParameters:
+    """The parameters of PDAL's filters.pmf / PCL's ProgressiveMorphologicalFilter (Zhang et al. 2003), with their usual defaults: the raster's
+    cell, the largest window (both in the units of the coordinates), the terrain slope, the height thresholds of the first and of the later
+    windows, and the growth of the windows' half-widths in cells: base^k (exponential) or (k + 1) * base."""
+    cell_size: float = 1.0
+    max_window_size: float = 33.0
+    slope: float = 1.0
+    initial_distance: float = 0.15
+    max_distance: float = 2.5
+    exponential: bool = True
+    base: int = 2
+
+    def c_args(self):
+        """the seven scalars the C entry points take, in their order"""
+        return (self.cell_size, self.max_window_size, self.slope, self.initial_distance, self.max_distance, 1 if self.exponential else 0, self.base)
+
+
+def pmf_schedule(params: PmfParameters = PmfParameters(), api=None):
+    """(half-widths in cells as uint32, thresholds as float64) of the windows `params` open the raster with.  Host only."""
+    from ._capi import product_api
+    h, th, count = np.zeros(32, dtype=np.uint32), np.zeros(32, dtype=np.float64), C.c_uint32()
+    (api or product_api()).pmf_schedule(*params.c_args(), h.ctypes.data_as(C.POINTER(C.c_uint32)), th.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count))
+    return h[:count.value].copy(), th[:count.value].copy()
+
+
+def pmf_grid(buffer: _Buffer, cell_size: float) -> dict:
+    """The raster ground_mask would lay over the finite points: origin (x0, y0), cols, rows, and the number of finite points (zeros without one)."""
+    origin, dim, finite = (C.c_double * 2)(), (C.c_uint32 * 2)(), C.c_uint64()
+    buffer.api.pmf_grid(buffer._h, cell_size, origin, dim, C.byref(finite))
+    return {"origin": (origin[0], origin[1]), "cols": dim[0], "rows": dim[1], "n_finite": finite.value}
+
+
+def ground_mask(buffer: _Buffer, params: PmfParameters = PmfParameters(), device_mask_ptr: Optional[int] = None, return_surfaces: bool = False):
+    """The progressive morphological ground filter on the device.  Returns (mask, n_ground[, surfaces]): mask is a numpy uint8 array (1 =
+    ground), or None when the len(buffer) bytes went to DEVICE memory at device_mask_ptr -- what filter takes as (ptr, 'device'); surfaces is
+    a dict of the three float64 (rows, cols) rasters "min_z" (+inf: empty cell), "opened" (the last opened surface) and "limit" (a point is
+    ground iff its z is not above its cell's limit), with the raster's "origin" (x0, y0) and "cell_size"."""
+    n = buffer.len()
+    mask = np.zeros(n, dtype=np.uint8) if device_mask_ptr is None else None
+    ptr = C.c_void_p(int(device_mask_ptr) or None) if mask is None else C.c_void_p(mask.ctypes.data if n else 1)
+    count = C.c_uint64()
+    surfaces, grid = None, None
+    if return_surfaces:
+        grid = pmf_grid(buffer, params.cell_size)
+        surfaces = np.full((3, grid["rows"], grid["cols"]), np.inf, dtype=np.float64)
+    sptr = C.c_void_p(surfaces.ctypes.data) if surfaces is not None and surfaces.size else None
+    buffer.api.pmf_ground_mask(buffer._h, *params.c_args(), ptr, 0 if mask is None else 1, sptr, 1, C.byref(count))
+    if not return_surfaces:
+        return mask, count.value
+    return mask, count.value, {"min_z": surfaces[0], "opened": surfaces[1], "limit": surfaces[2], "origin": grid["origin"], "cell_size": params.cell_size}
+
+
+def finite_mask(buffer: _Buffer, device_mask_ptr: int) -> None:
+    """Stream-ordered: len(buffer) bytes in DEVICE memory, 1 where x, y and z of the Position3D are all finite."""
+    buffer.api.finite_mask_device(buffer._h, C.c_void_p(int(device_mask_ptr) or None))
+
+
+def set_u8_where(buffer: _Buffer, attribute: PointAttributeDefinition, device_mask_ptr: int, value: int) -> None:
+    """Stream-ordered: the U8 attribute = value wherever the byte of the DEVICE mask is not zero; the other points keep theirs."""
+    buffer.api.buffer_set_u8_where_device(buffer._h, attribute.name().encode(), C.c_void_p(int(device_mask_ptr) or None), value)
+
+
+def classify_ground(buffer: _Buffer, params: PmfParameters = PmfParameters(), ground_class: int = 2, other_class: Optional[int] = None) -> int:
+    """Writes the LAS Classification (U8) of `buffer` in place on the device: ground_class (2 in the LAS specification) for the ground points;
+    other_class for every other point, or, with None, whatever class they have.  Returns the number of ground points."""
+    from .layout import PointAttributeDataType as T, attributes as A
+    n = buffer.len()
+    if n == 0:  # (the call's own checks of the parameters and the layout, answered on the host)
+        set_u8_where(buffer, A.CLASSIFICATION, 0, ground_class)
+        return ground_mask(buffer, params)[1]
+    mask = _DeviceArray(buffer.api, T.U8, n)
+    ground = ground_mask(buffer, params, device_mask_ptr=mask.ptr or 1)[1]
+    if other_class is not None and n:  # every point first, through a mask of ones (one byte per point from the host: the library has no fill entry point)
+        ones = _DeviceArray(buffer.api, T.U8, n)
+        ones.buffer.set_attribute_range(ones.attribute, range(0, n), np.ones(n, dtype=np.uint8))
+        set_u8_where(buffer, A.CLASSIFICATION, ones.ptr, other_class)
+    set_u8_where(buffer, A.CLASSIFICATION, mask.ptr, ground_class)
+    buffer.api.stream_synchronize()  # (the mask is released when this returns)
+    return ground
+
+
+def extract_ground(buffer: _Buffer, params: PmfParameters = PmfParameters(), out_buffer_type=None):
+    """(the ground points in buffer order with all their attributes, their number): mask and compaction stay in device memory.  `buffer` is
+    columnar (filter is defined on HashMapBuffer)."""
+    return _filter_by_device_mask(buffer, out_buffer_type, lambda p: ground_mask(buffer, params, device_mask_ptr=p or 1)[1])
+
+
+def remove_ground(buffer: _Buffer, params: PmfParameters = PmfParameters(), out_buffer_type=None):
+    """(the FINITE points that are not ground, the number of ground points): with extract_ground's result a partition of the finite points."""
+    from .layout import PointAttributeDataType as T
+    ground = _DeviceArray(buffer.api, T.U8, buffer.len())
+
+    def fill(keep):  # finite, then cleared where ground
+        count = ground_mask(buffer, params, device_mask_ptr=ground.ptr or 1)[1]
+        finite_mask(buffer, keep.ptr)
+        set_u8_where(keep.buffer, keep.attribute, ground.ptr, 0)
+        return count
+    return _filter_by_device_mask(buffer, out_buffer_type, fill, whole_array=True)
+
+
+def _grid_morphology(op: int, device_in_ptr: int, device_out_ptr: int, cols: int, rows: int, half_width: int, api=None) -> None:
+    from ._capi import product_api
+    (api or product_api()).grid_morphology_device(C.c_void_p(int(device_in_ptr) or None), C.c_void_p(int(device_out_ptr) or None), cols, rows, half_width, op)
+
+
+def grid_erode(device_in_ptr: int, device_out_ptr: int, cols: int, rows: int, half_width: int, api=None) -> None:
+    """Stream-ordered, not in place: out[r][c] = the minimum of the float64 (rows, cols) raster at device_in_ptr over the square of half_width
+    cells around (r, c), clipped to the raster.  Entries are finite or +inf."""
+    _grid_morphology(0, device_in_ptr, device_out_ptr, cols, rows, half_width, api)
+
+
+def grid_dilate(device_in_ptr: int, device_out_ptr: int, cols: int, rows: int, half_width: int, api=None) -> None:
+    """As grid_erode, with the maximum over the entries below +inf (+inf where the square holds none)."""
+    _grid_morphology(1, device_in_ptr, device_out_ptr, cols, rows, half_width, api)
+
+
+def pmf_kernel_shape(api=None) -> dict:
+    """The seams of the ground filter's kernels: points per workgroup of the point passes, columns and rows of a morphology tile, the largest
+    half-width of one morphology pass."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(4)]
+    (api or product_api()).pmf_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "tile_cols", "tile_rows", "max_half_width"), (x.value for x in v)))
+
+
+def pmf_phase_times(api=None):
+    """(bounds + raster, morphology, classification) in milliseconds of this thread's last ground_mask call; zeros unless PST_PMF_TIMES=1 was
+    set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).pmf_phase_times(ms)
     return tuple(ms)
 
 

@@ -41,12 +41,6 @@ constexpr uint32_t kBoundsPoints = 1024;  // points per workgroup of the bounds 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 static_assert(kP == kBlock, "one lane per point");
 
-// order-preserving map of the finite doubles onto unsigned integers (-0.0 below +0.0)
-__device__ __forceinline__ unsigned long long ordered(double v) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 using Record = pstk::ClusterRecord;
 using Grid = pstk::ClusterGrid;
 
@@ -245,10 +239,7 @@ bool cluster_bounds(const Positions& pos, ClusterRecord* rec, hipStream_t stream
   return launched();
 }
 
-double cluster_decode_ordered(unsigned long long v) {
-  const unsigned long long u = (v >> 63) ? (v & 0x7FFFFFFFFFFFFFFFull) : ~v;
-  return __builtin_bit_cast(double, u);
-}
+double cluster_decode_ordered(unsigned long long v) { return decode_ordered(v); }
 
 bool cluster_keys(const Positions& pos, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream) {
   hipLaunchKernelGGL(cluster_key_kernel, dim3(blocks_of(pos.n, kBlock)), dim3(kBlock), 0, stream, pos_of(pos), pos.n, g, keys, vals);

@@ -239,6 +239,34 @@ bool cluster_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, u
                     uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, hipStream_t stream);
 bool cluster_mask(const uint32_t* labels, uint64_t n, uint32_t first_cluster, uint32_t cluster_count, uint8_t* mask, hipStream_t stream);
 
+// Ground classification by the progressive morphological filter (pmf.hip; the schedule, the grid and the order of the passes are in pmf_api.cpp).
+// The seams (pst_pmf_kernel_shape):
+constexpr uint32_t kPmfPointsPerBlock = 1024;  // points per workgroup of the raster, classification and set-where passes, four per lane
+constexpr uint32_t kPmfTileCols = 64;          // raster cells one workgroup of a morphology pass writes: one wave per tile row ...
+constexpr uint32_t kPmfTileRows = 32;          // ... eight rows per wave
+// Largest half-width of ONE morphology pass.  The LDS tile of a pass carries a halo of that many cells on both sides of the axis it works
+// along: (kPmfTileRows + 2 H) x kPmfTileCols doubles for the column pass, the larger of the two.  H = 32 makes that 96 x 64 x 8 = 48 KiB:
+// static LDS (below 64 KiB), three workgroups per compute unit of its 160 KiB, and every window of the default schedule (up to 16) one pass.
+constexpr uint32_t kPmfMaxHalfWidth = 32;
+constexpr uint32_t kPmfMaxWindows = 32;
+// the raster: cell (row, col) of a point = (trunc((y - y0) / cell), trunc((x - x0) / cell)), rows x cols cells, row-major with col fastest
+struct PmfGrid { double x0, y0, cell; uint32_t cols, rows; };
+// cells[row * cols + col] = min over the finite points of the cell of the ordered encoding of z; the caller has set every byte of `cells`
+bool pmf_raster(const Positions& pos, const PmfGrid& g, unsigned long long* cells, hipStream_t stream);
+// One separable pass, out of place: out[r][c] = min (dilate: max over the entries below +inf, +inf without one) of in over |d| <= h along
+// the columns (axis 0) or the rows (axis 1), clipped to the raster; h <= kPmfMaxHalfWidth.  in_is_keys: `in` holds pmf_raster's keys (all
+// ones = +inf).  fold 1: also L[cell] = out + th; fold 2: L[cell] = min(L[cell], out + th).
+bool pmf_morphology_pass(const void* in, bool in_is_keys, double* out, uint32_t cols, uint32_t rows, uint32_t h, bool dilate, int axis, double* L, int fold,
+                         double th, hipStream_t stream);
+// keys to doubles in place (all ones = +inf)
+bool pmf_decode_keys(unsigned long long* cells, uint64_t n_cells, hipStream_t stream);
+// mask[i] = 1 iff point i is finite and z <= L[its cell]; *count += the ones (one integer atomic per workgroup)
+bool pmf_classify(const Positions& pos, const PmfGrid& g, const double* L, uint8_t* mask, unsigned long long* count, hipStream_t stream);
+// mask[i] = 1 iff x, y and z of point i are finite
+bool finite_mask(const Positions& pos, uint8_t* mask, hipStream_t stream);
+// the byte at addr + i * stride = value wherever mask[i] != 0, i < n
+bool set_u8_where(uint64_t addr, uint64_t stride, uint64_t n, const uint8_t* mask, uint8_t value, hipStream_t stream);
+
 // Nearest neighbours between two clouds and the sums of an ICP step (nn.hip; the index and the ICP loop are in nn_api.cpp).  The seams
 // (pst_nn_kernel_shape):
 constexpr uint32_t kNnQueriesPerBlock = 256;  // queries one workgroup of the search kernel owns, one lane each; candidates are not staged in LDS

@@ -16,6 +16,17 @@ __device__ __forceinline__ void load_point(const Pos& p, uint64_t i, double& x, 
 }
 __device__ __forceinline__ bool finite(double v) { return __builtin_fabs(v) < kInf; }  // false for a NaN
 
+// order-preserving map of the finite doubles onto unsigned integers (-0.0 below +0.0), and back: what the integer atomicMin / atomicMax of
+// clusters.hip (the AABB) and pmf.hip (the AABB, the min-z raster) fold
+__host__ __device__ __forceinline__ unsigned long long ordered(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__host__ __device__ __forceinline__ double decode_ordered(unsigned long long v) {
+  const unsigned long long u = (v >> 63) ? (v & 0x7FFFFFFFFFFFFFFFull) : ~v;
+  return __builtin_bit_cast(double, u);
+}
+
 inline unsigned blocks_of(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }
 inline bool launched() { return hipGetLastError() == hipSuccess; }
 
