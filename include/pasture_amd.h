@@ -674,6 +674,61 @@ int pst_nn_kernel_shape(uint32_t* queries_per_block, uint32_t* reduce_block, uin
  * returns the calling thread's last call: ms = {query keys + sort, search}.  Zeros without the switch.  Host only. */
 int pst_nn_phase_times(double ms[2]);
 
+/* ---- Height above ground -----------------------------------------------------------------------------------------------------------------
+ * What PDAL's filters.hag_nn and lidR's normalize_height(knnidw()) compute (the reference has neither): for every point of a QUERY cloud
+ * the elevation of the ground under it, interpolated from its k nearest GROUND points IN THE XY PLANE with inverse squared distance
+ * weights, and the point's height above it.  The definitions:
+ *   ground set:   G = the points of the `ground` buffer whose Position3D (Vec3f64) has three finite components and whose mask byte is not
+ *                 zero; a NULL mask means every point of the buffer.  Points of `ground` that are not finite or not masked are never
+ *                 neighbours.
+ *   queries:      every point of the `query` buffer; `query` and `ground` may be the same buffer.  A query is finite when its three
+ *                 components are.
+ *   distance:     d2(q, p) = dx*dx + dy*dy, dx = p.x - q.x, dy = p.y - q.y: z takes no part.  Every operation here and below is a
+ *                 separately rounded f64 operation (no contraction); no square root appears anywhere.
+ *   neighbours:   of a finite query, the at most k members of G with the lexicographically smallest (d2, ground-buffer index) among those
+ *                 with d2 <= m2, m2 = max_distance * max_distance rounded once on the host (+inf: unbounded); in that order
+ *                 (d2_0, z_0), ..., (d2_{j-1}, z_{j-1}), 0 <= j <= k.  A query that is not finite has none.
+ *   elevation:    w_i = 1.0 / d2_i (inverse SQUARED distance, as in filters.hag_nn).  If w_0 is not below +inf -- d2_0 is 0, or so small
+ *                 that its reciprocal overflows -- the query has an exact hit and zg = z_0.  Otherwise num = w_0*z_0, then
+ *                 num = num + w_i*z_i for i = 1 .. j-1 in that order; den = w_0, then den = den + w_i in that order; zg = num / den.
+ *                 Nothing else is special-cased: what IEEE arithmetic gives is the definition (a neighbour at d2 = +inf of an unbounded
+ *                 search has weight 0, and a query all of whose neighbours have gets 0 / 0).
+ *   results:      ground_z[i] = zg, hag[i] = q.z - zg.  j = 0 gives NaN in both: no ground within max_distance, an empty or all-masked-out
+ *                 G, a query that is not finite.
+ *   same buffer:  there is no special case for queries that are themselves ground: with query == ground a ground point finds itself at
+ *                 d2 = 0 and gets hag = +0.0 -- EXCEPT when a lower-indexed member of G shares its x and y: that one is the exact hit, and
+ *                 the point gets its height over it.
+ *   max_distance: validated exactly as pst_nearest_neighbours_device validates it.
+ * The result is a function of the two clouds, the mask, k and max_distance alone: not of the grid, not of the order in which the search
+ * visits cells, not of the storage kind.
+ * Checks: null arguments and invalid parameters (k == 0 or k > max_k = 32; max_distance; a negative, NaN or infinite cell_edge; d_hag and
+ * d_ground_z both NULL) are answered before a device is looked for; then PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64
+ * in either buffer; an empty `query` is then PST_OK on the host with nothing written and zeros in the counts and the grid; then the device
+ * (none: PST_ERR_NO_DEVICE, never a CPU path); then the lengths: 2^32 - 16 points and more in either buffer -> PST_ERR_UNSUPPORTED.  Out of
+ * device memory is PST_ERR_OUT_OF_MEMORY and the next call works.  An empty or all-masked `ground` writes NaN everywhere, sets n_unresolved
+ * to the number of finite queries and reports a zero grid.
+ * Synchronous (the host reads G's bounds to size the grid).  The index -- G sorted into a uniform XY grid over its AABB with a dense cell
+ * directory, 4 bytes per cell -- is rebuilt by every call in the call's scratch.  cell_edge > 0: the grid's cell edge; 0: chosen so that
+ * the 3 x 3 cells around a query hold about 2k ground points if G filled its rectangle.  Either is doubled until no axis has more than
+ * 2^21 - 1 cells and the grid no more than 2^26.  d_hag, d_ground_z: DEVICE memory, len(query) x f64, either may be NULL, not both.
+ * d_ground_mask: DEVICE memory, len(ground) bytes, or NULL.  n_ground = |G|, n_unresolved = the finite queries with j == 0,
+ * grid_min_and_edge = {min x, min y, final cell edge} and grid_dim = {columns, rows} of the grid that was used: each optional, host.
+ * Cost: a query tests the ground points of the 3 x 3 cells around its own and goes on ring by ring only while its k-th best distance
+ * exceeds the rings searched; ring r costs O(r) directory reads.  max_distance bounds the walk. */
+int pst_height_above_ground_device(const pst_buffer* query, const pst_buffer* ground, const uint8_t* d_ground_mask, uint32_t k, double max_distance, double cell_edge,
+                                   double* d_hag, double* d_ground_z, uint64_t* n_ground, uint64_t* n_unresolved, double grid_min_and_edge[3], uint32_t grid_dim[2]);
+/* The inverse of pst_buffer_set_u8_where_device: d_mask[i] = 1 iff the U8 attribute of point i equals `value`, else 0 (DEVICE memory,
+ * len(b) bytes).  Stream-ordered, no host synchronisation: how Classification == 2 becomes a ground mask without a host round trip.  An
+ * attribute the layout does not have as U8 is PST_ERR_MISSING_ATTRIBUTE; an empty buffer is PST_OK on the host. */
+int pst_buffer_u8_equals_mask_device(const pst_buffer* b, const char* attribute_name, uint8_t value, uint8_t* d_mask);
+/* The kernels' seams (each pointer optional; host only): queries one workgroup of the search kernel owns (one lane each), the largest k,
+ * ground points per block partial of the masked bounds. */
+int pst_hag_kernel_shape(uint32_t* queries_per_block, uint32_t* max_k, uint32_t* bounds_points_per_block);
+/* Measurement aid.  With PST_HAG_TIMES=1 in the environment pst_height_above_ground_device brackets its three phases with stream events;
+ * this returns the calling thread's last call: ms = {ground bounds + keys + sort + directory, query keys + sort, search}.  Zeros without the
+ * switch.  Host only. */
+int pst_hag_phase_times(double ms[3]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -811,3 +811,97 @@ def nn_phase_times(api=None):
     ms = (C.c_double * 2)()
     (api or product_api()).nn_phase_times(ms)
     return tuple(ms)
+
+
+# ---- height above ground from the k nearest ground points in the XY plane (include/pasture_amd.h) ---------------------------------------------
+
+def classification_mask(buffer: _Buffer, value: int, device_mask_ptr: int) -> None:
+    """Stream-ordered: len(buffer) bytes in DEVICE memory, 1 where the LAS Classification (U8) equals `value` -- the inverse of what
+    classify_ground writes, and the ground mask of height_above_ground without a host round trip."""
+    from .layout import attributes as A
+    buffer.api.buffer_u8_equals_mask_device(buffer._h, A.CLASSIFICATION.name().encode(), value, C.c_void_p(int(device_mask_ptr) or None))
+
+
+def height_above_ground_device(buffer: _Buffer, device_ground_mask_ptr: Optional[int] = None, k: int = 1, max_distance: float = float("inf"), ground: Optional[_Buffer] = None,
+                               cell_edge: float = 0.0, hag_ptr: int = 0, ground_z_ptr: int = 0) -> dict:
+    """PDAL's filters.hag_nn on the device: for every point of `buffer` the elevation of the ground under it -- the inverse squared distance
+    weighted mean of the z of its k nearest ground points IN THE XY PLANE within max_distance -- and its height above it, as float64 in
+    caller-owned DEVICE memory (addresses; 0 = not wanted, not both).  The ground points are those of `ground` (None: `buffer` itself) whose
+    byte in the DEVICE mask at device_ground_mask_ptr is not zero (None or 0: every finite point of it).  Returns {"n_ground",
+    "n_unresolved" (finite points without a ground point in reach: NaN), "origin", "cell_edge", "dim"} -- the last three describe the grid
+    that was used, which the result does not depend on."""
+    ng, nu, me, dim = C.c_uint64(), C.c_uint64(), (C.c_double * 3)(), (C.c_uint32 * 2)()
+    g = buffer if ground is None else ground
+    buffer.api.height_above_ground_device(buffer._h, g._h, C.c_void_p(int(device_ground_mask_ptr or 0) or None), k, max_distance, cell_edge, C.c_void_p(hag_ptr or None),
+                                          C.c_void_p(ground_z_ptr or None), C.byref(ng), C.byref(nu), me, dim)
+    return {"n_ground": ng.value, "n_unresolved": nu.value, "origin": (me[0], me[1]), "cell_edge": me[2], "dim": (dim[0], dim[1])}
+
+
+def _ground_mask_array(buffer: _Buffer, ground: Optional[_Buffer], ground_mask):
+    """(the _DeviceArray that keeps an uploaded or computed mask alive, or None; the mask's device address, or None)"""
+    from .layout import PointAttributeDataType as T
+    g = buffer if ground is None else ground
+    if ground_mask is None:  # Classification == 2
+        held = _DeviceArray(g.api, T.U8, g.len())
+        classification_mask(g, 2, held.ptr)
+        return held, held.ptr
+    if isinstance(ground_mask, (int, np.integer)):
+        return None, int(ground_mask)
+    m = np.ascontiguousarray(ground_mask, dtype=np.uint8)
+    if m.shape != (g.len(),):
+        raise ValueError("ground_mask must have one byte per point of the ground buffer")
+    held = _DeviceArray(g.api, T.U8, g.len())
+    if g.len():
+        held.buffer.set_attribute_range(held.attribute, range(0, g.len()), m)
+    return held, held.ptr
+
+
+def height_above_ground(buffer: _Buffer, ground_mask=None, k: int = 1, max_distance: float = float("inf"), ground: Optional[_Buffer] = None, cell_edge: float = 0.0,
+                        return_ground_z: bool = False):
+    """Height above ground of every point of `buffer` as numpy float64 (n,), or (hag, ground_z) with return_ground_z: see
+    height_above_ground_device.  ground_mask: a numpy uint8 array with one byte per point of the ground buffer (uploaded), the address of
+    such bytes in DEVICE memory, or None for Classification == 2 (what classify_ground writes).  ground = None: the buffer itself.  Points
+    without a ground point within max_distance, and points that are not finite, get NaN."""
+    from .layout import PointAttributeDataType as T
+    n = buffer.len()
+    held, mask_ptr = _ground_mask_array(buffer, ground, ground_mask)
+    hag = _DeviceArray(buffer.api, T.F64, n)
+    gz = _DeviceArray(buffer.api, T.F64, n) if return_ground_z else None
+    height_above_ground_device(buffer, mask_ptr, k, max_distance, ground, cell_edge, hag.ptr or 1, (gz.ptr or 1) if gz else 0)
+    del held
+    return (hag.to_numpy(), gz.to_numpy()) if return_ground_z else hag.to_numpy()
+
+
+def normalize_height(buffer: _Buffer, ground_mask=None, k: int = 1, max_distance: float = float("inf"), ground: Optional[_Buffer] = None, cell_edge: float = 0.0) -> int:
+    """lidR's normalize_height(knnidw()): replaces the z of every Position3D of `buffer` IN PLACE by its height above ground, computed and
+    written on the device (x and y keep their bits).  Returns n_unresolved: that many finite points had no ground point within
+    max_distance; their z, like that of every point that is not finite, becomes NaN.  With the buffer as its own ground the ground mask is
+    taken BEFORE z changes; the ground points themselves end at height +0.0."""
+    from .layout import PointAttributeDataType as T, attributes as A
+    n = buffer.len()
+    held, mask_ptr = _ground_mask_array(buffer, ground, ground_mask)
+    hag = _DeviceArray(buffer.api, T.F64, n)
+    info = height_above_ground_device(buffer, mask_ptr, k, max_distance, ground, cell_edge, hag.ptr or 1)
+    if n:
+        transform_attribute_expr(buffer, A.POSITION_3D, "x ; y ; p0[i]", [hag.ptr])
+        buffer.api.stream_synchronize()  # (the heights are released when this returns)
+    del held
+    return info["n_unresolved"]
+
+
+def hag_kernel_shape(api=None) -> dict:
+    """The seams of the height-above-ground kernels: queries one workgroup of the search owns, the largest k, ground points per block partial
+    of the masked bounds."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).hag_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("queries_per_block", "max_k", "bounds_points_per_block"), (x.value for x in v)))
+
+
+def hag_phase_times(api=None):
+    """(ground bounds + keys + sort + directory, query keys + sort, search) in milliseconds of this thread's last height_above_ground* call;
+    zeros unless PST_HAG_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).hag_phase_times(ms)
+    return tuple(ms)

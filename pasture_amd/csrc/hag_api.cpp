@@ -1,0 +1,193 @@
+// pst_height_above_ground_device / pst_buffer_u8_equals_mask_device / pst_hag_kernel_shape / pst_hag_phase_times: argument checks, the grid
+// (hag_grid.hpp), the scratch layout and the order of the launches of hag.hip (where the definitions and the ring argument are).
+#include <cmath>
+#include <cstring>
+
+#include "device_sort.hpp"
+#include "runtime.hpp"
+
+using namespace pst;
+
+namespace {
+
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
+
+// PST_HAG_TIMES=1: stream events around the three phases of every call (tools/bench_hag.py reads them through pst_hag_phase_times)
+struct PhaseEvents {
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool on;
+  PhaseEvents() {
+    static const bool wanted = env_nonzero("PST_HAG_TIMES");
+    on = wanted;
+    if (on)
+      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
+  }
+  ~PhaseEvents() {
+    for (auto ev : e)
+      if (ev) (void)hipEventDestroy(ev);
+  }
+  void mark(int i, hipStream_t s) {
+    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
+  }
+  void read() {  // after the stream has been synchronised
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0.f;
+      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
+      t_phase_ms[i] = ms;
+    }
+  }
+};
+
+const Member& position_member(const pst_buffer& b) {
+  const Member* m = position_vec3f64(b);
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  return *m;
+}
+
+// the masked bounds of G, read back (two launches, one synchronisation).  Their block partials are needed before the grid -- and with it the
+// size of the call's scratch -- is known: they live in a small block of their own, like the bounds record of pmf_api.cpp.
+pstk::HagBounds ground_bounds(const pstk::Positions& ground, const uint8_t* mask, hipStream_t s, const char* who) {
+  ScratchLayout layout;
+  const size_t off_partials = layout.add(pstk::hag_bounds_partials_bytes(ground.n)), off_rec = layout.add(sizeof(pstk::HagBounds));
+  Scratch block(layout, s, who);
+  pstk::HagBounds* rec = block.at<pstk::HagBounds>(off_rec);
+  if (!pstk::hag_bounds(ground, mask, block.at<void>(off_partials), rec, s)) throw hip_failure(std::string(who) + ": bounds launch failed: ");
+  pstk::HagBounds r{};
+  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pst_hag_kernel_shape(uint32_t* queries_per_block, uint32_t* max_k, uint32_t* bounds_points_per_block) {
+  if (queries_per_block) *queries_per_block = pstk::kHagQueriesPerBlock;
+  if (max_k) *max_k = pstk::kHagMaxK;
+  if (bounds_points_per_block) *bounds_points_per_block = pstk::kHagBoundsPointsPerBlock;
+  return PST_OK;
+}
+
+int pst_hag_phase_times(double ms[3]) {
+  PST_API_BEGIN
+  not_null(ms, "ms");
+  std::memcpy(ms, t_phase_ms, sizeof(t_phase_ms));
+  PST_API_END
+}
+
+int pst_height_above_ground_device(const pst_buffer* query, const pst_buffer* ground, const uint8_t* d_ground_mask, uint32_t k, double max_distance, double cell_edge,
+                                   double* d_hag, double* d_ground_z, uint64_t* n_ground, uint64_t* n_unresolved, double grid_min_and_edge[3], uint32_t grid_dim[2]) {
+  PST_API_BEGIN
+  const char* who = "pst_height_above_ground_device";
+  not_null(query, "query");
+  not_null(ground, "ground");
+  if (!d_hag && !d_ground_z) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": d_hag and d_ground_z must not both be NULL");
+  if (k == 0 || k > pstk::kHagMaxK) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": k must be between 1 and 32");
+  const double m2 = checked_m2(max_distance, who);
+  if (!(cell_edge >= 0.0) || std::isinf(cell_edge)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": cell_edge must be finite and not negative (0: automatic)");
+  const Member& qm = position_member(*query);
+  const Member& gm = position_member(*ground);
+  if (n_ground) *n_ground = 0;
+  if (n_unresolved) *n_unresolved = 0;
+  if (grid_min_and_edge) grid_min_and_edge[0] = grid_min_and_edge[1] = grid_min_and_edge[2] = 0.0;
+  if (grid_dim) grid_dim[0] = grid_dim[1] = 0;
+  const size_t nq = query->len, ng_points = ground->len;
+  if (nq == 0) return PST_OK;  // no query: nothing to write
+  ensure_device();
+  if (nq >= 0xFFFFFFF0ull || ng_points >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+
+  hipStream_t s = current_stream();
+  const pstk::Positions qpos = positions_of(*query, qm), gpos = positions_of(*ground, gm);
+  PhaseEvents events;
+  events.mark(0, s);
+  pstk::HagBounds bounds{};
+  if (ng_points) bounds = ground_bounds(gpos, d_ground_mask, s, who);
+  const uint32_t ng = (uint32_t)bounds.count;
+  unsigned long long unresolved = 0;
+
+  if (ng == 0) {  // no ground: NaN everywhere, every finite query is unresolved, a zero grid
+    Scratch block;
+    unsigned long long* count = block.alloc<unsigned long long>(256, s, who);
+    PST_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(*count), s));
+    for (int i = 1; i < 3; ++i) events.mark(i, s);
+    if (!pstk::hag_fill_unresolved(qpos, d_hag, d_ground_z, count, s)) throw hip_failure(std::string(who) + ": fill launch failed: ");
+    events.mark(3, s);
+    PST_HIP_CHECK(hipMemcpyAsync(&unresolved, count, sizeof(unresolved), hipMemcpyDeviceToHost, s));
+    stream_sync(s);
+    events.read();
+    if (n_unresolved) *n_unresolved = unresolved;
+    return PST_OK;
+  }
+
+  pstk::HagGrid grid{};
+  const double edge = cell_edge > 0.0 ? cell_edge : pstk::hag_auto_edge(ng, bounds.max_x - bounds.min_x, bounds.max_y - bounds.min_y, k);
+  if (!pstk::hag_make_grid(bounds.min_x, bounds.min_y, bounds.max_x, bounds.max_y, edge, &grid))
+    throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": the extent of the ground points overflows f64");
+  const size_t cells = (size_t)grid.dim[0] * grid.dim[1];
+  const unsigned key_bits = grid.bits[0] + grid.bits[1] + 1;  // (the bit above the cell number: not in G / not finite)
+
+  // One block of scratch.  The three arrays a sort alternates between serve the ground sort and then the query sort (the gather and the
+  // directory are done with them by then, in stream order): keys a | keys b | values a, each max(len(ground), len(query)) words; then the
+  // ground order = the buffer index of every sorted position | x | y | z of G | the directory | the query order | sort and scan scratch |
+  // the unresolved count.
+  const size_t n_max = std::max(nq, ng_points);
+  size_t sort_g = 0, sort_q = 0, scan_bytes = 0;
+  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_g, nullptr, nullptr, nullptr, nullptr, ng_points, key_bits, s, true));
+  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_q, nullptr, nullptr, nullptr, nullptr, nq, key_bits, s));
+  PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, scan_bytes, nullptr, cells + 1, s));
+  ScratchLayout layout;
+  const size_t off_keys_a = layout.add(n_max * 4), off_keys_b = layout.add(n_max * 4), off_vals_a = layout.add(n_max * 4), off_gorder = layout.add(ng_points * 4);
+  const size_t off_xs = layout.add((size_t)ng * 8), off_ys = layout.add((size_t)ng * 8), off_zs = layout.add((size_t)ng * 8), off_dir = layout.add((cells + 1) * 4);
+  const size_t off_qorder = layout.add(nq * 4), off_tmp = layout.add(std::max(std::max(sort_g, sort_q), scan_bytes)), off_count = layout.add(256);
+  Scratch scratch(layout, s, who);
+  uint32_t *keys_a = scratch.at<uint32_t>(off_keys_a), *keys_b = scratch.at<uint32_t>(off_keys_b), *vals_a = scratch.at<uint32_t>(off_vals_a);
+  uint32_t *gorder = scratch.at<uint32_t>(off_gorder), *dir = scratch.at<uint32_t>(off_dir), *qorder = scratch.at<uint32_t>(off_qorder);
+  double *xs = scratch.at<double>(off_xs), *ys = scratch.at<double>(off_ys), *zs = scratch.at<double>(off_zs);
+  void* tmp = scratch.at<void>(off_tmp);
+  unsigned long long* count = scratch.at<unsigned long long>(off_count);
+
+  // ---- the ground index
+  PST_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(*count), s));
+  PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (cells + 1) * 4, s));
+  if (!pstk::hag_ground_keys(gpos, d_ground_mask, grid, keys_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
+  size_t bytes = sort_g;
+  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, gorder, ng_points, key_bits, s, true));
+  if (!pstk::hag_gather(gpos, gorder, ng, xs, ys, zs, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");
+  if (!pstk::hag_directory_heads(keys_b, ng, grid, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
+  bytes = scan_bytes;
+  PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, cells + 1, s));
+  events.mark(1, s);
+  // ---- the queries in cell order
+  if (!pstk::hag_query_keys(qpos, grid, keys_a, vals_a, s)) throw hip_failure(std::string(who) + ": query key launch failed: ");
+  bytes = sort_q;
+  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, qorder, nq, key_bits, s));
+  events.mark(2, s);
+  // ---- the search
+  if (!pstk::hag_search(qpos, grid, k, m2, keys_b, qorder, dir, xs, ys, zs, gorder, d_hag, d_ground_z, count, s)) throw hip_failure(std::string(who) + ": search launch failed: ");
+  events.mark(3, s);
+  PST_HIP_CHECK(hipMemcpyAsync(&unresolved, count, sizeof(unresolved), hipMemcpyDeviceToHost, s));
+  stream_sync(s);
+  events.read();
+  if (n_ground) *n_ground = ng;
+  if (n_unresolved) *n_unresolved = unresolved;
+  if (grid_min_and_edge) { grid_min_and_edge[0] = grid.min[0]; grid_min_and_edge[1] = grid.min[1]; grid_min_and_edge[2] = grid.edge; }
+  if (grid_dim) { grid_dim[0] = grid.dim[0]; grid_dim[1] = grid.dim[1]; }
+  PST_API_END
+}
+
+int pst_buffer_u8_equals_mask_device(const pst_buffer* b, const char* attribute_name, uint8_t value, uint8_t* d_mask) {
+  PST_API_BEGIN
+  not_null(b, "buffer");
+  not_null(attribute_name, "attribute_name");
+  const Member* m = b->layout.find(AttributeDef{attribute_name, DataType{}});  // (a default datatype is U8)
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  if (b->len == 0) return PST_OK;
+  not_null(d_mask, "d_mask");
+  ensure_device();
+  const AttrView v = attr_view(*b, m);
+  if (!pstk::u8_equals_mask(v.addr, v.stride, b->len, value, d_mask, current_stream())) throw hip_failure("equals-mask launch failed: ");
+  PST_API_END
+}
+
+}  // extern "C"

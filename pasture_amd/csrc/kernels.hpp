@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/pasture_amd.h"
+#include "hag_grid.hpp"
 #include "plan.h"
 
 namespace pstk {
@@ -302,5 +303,35 @@ bool nn_gather_normals(const uint8_t* base, uint64_t stride, bool is_f32, const 
 size_t nn_plane_partials_bytes(uint64_t n);
 bool nn_plane_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double* nx,
                    const double* ny, const double* nz, const double origin[3], void* partials, NnPlaneSums* rec, hipStream_t stream);
+
+// Height above ground from the k nearest ground points in the XY plane (hag.hip; the grid is sized in hag_grid.hpp, the scratch and the order
+// of the launches are in hag_api.cpp).  The seams (pst_hag_kernel_shape):
+constexpr uint32_t kHagQueriesPerBlock = 64;       // queries one workgroup of the search kernel owns: ONE wave, one lane per query
+constexpr uint32_t kHagMaxK = 32;                  // the k-best list lives in LDS, 16 bytes per slot and lane: 32 KiB per workgroup at the most
+constexpr uint32_t kHagBoundsPointsPerBlock = 4096;  // ground points per block partial of the masked bounds, sixteen per lane
+// the device-side record of the masked 2-D bounds: the AABB of G in x and y, |G|
+struct HagBounds { double min_x, min_y, max_x, max_y; unsigned long long count; };
+size_t hag_bounds_partials_bytes(uint64_t n_ground_points);
+// G = the points whose three components are finite and whose mask byte is not zero (mask == nullptr: every finite point).  Block partials,
+// then one workgroup folds them into *rec; no atomics.  An empty G leaves {+inf, +inf, -inf, -inf, 0}.
+bool hag_bounds(const Positions& ground, const uint8_t* mask, void* partials, HagBounds* rec, hipStream_t stream);
+// keys[i] = (cy << bits[0]) | cx of ground point i, with bit bits[0] + bits[1] set when i is not in G
+bool hag_ground_keys(const Positions& ground, const uint8_t* mask, const HagGrid& g, uint32_t* keys, hipStream_t stream);
+// positions of the ng members of G in sorted order
+bool hag_gather(const Positions& ground, const uint32_t* order, uint32_t ng, double* xs, double* ys, double* zs, hipStream_t stream);
+// dir: cols * rows + 1 entries, every byte 0xFF on entry.  dir[cell] = first sorted position of every occupied cell, dir[cols * rows] = ng;
+// pstk::suffix_min_u32 over all of it then makes dir[c] the first sorted position whose cell is c or later
+bool hag_directory_heads(const uint32_t* sorted_keys, uint32_t ng, const HagGrid& g, uint32_t* dir, hipStream_t stream);
+// keys[i] = the key of query i's cell after its x and y were clamped into the grid's AABB; bit bits[0] + bits[1] alone: not finite.  vals[i] = i
+bool hag_query_keys(const Positions& query, const HagGrid& g, uint32_t* keys, uint32_t* vals, hipStream_t stream);
+// The search.  query_keys / query_order: the sorted pairs.  hag[i] = q.z - zg, ground_z[i] = zg (each optional); *unresolved += the finite
+// queries without a neighbour.  k <= kHagMaxK.
+bool hag_search(const Positions& query, const HagGrid& g, uint32_t k, double m2, const uint32_t* query_keys, const uint32_t* query_order, const uint32_t* dir,
+                const double* xs, const double* ys, const double* zs, const uint32_t* ground_index, double* hag, double* ground_z, unsigned long long* unresolved,
+                hipStream_t stream);
+// no ground at all: NaN into both outputs, *unresolved += the finite queries
+bool hag_fill_unresolved(const Positions& query, double* hag, double* ground_z, unsigned long long* unresolved, hipStream_t stream);
+// mask[i] = 1 iff the byte at addr + i * stride equals value, i < n
+bool u8_equals_mask(uint64_t addr, uint64_t stride, uint64_t n, uint8_t value, uint8_t* mask, hipStream_t stream);
 
 }  // namespace pstk

@@ -115,13 +115,6 @@ struct CheckedTransform {
   }
 };
 
-double checked_m2(double max_distance, const char* who) {
-  const double m2 = max_distance * max_distance;
-  if (std::isnan(max_distance) || !(max_distance > 0.0) || !(std::isnormal(m2) || std::isinf(m2)))
-    throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": max_distance must be positive (+inf: unbounded), and its square a normal number or +inf");
-  return m2;
-}
-
 const Member& position_member(const pst_buffer& b) {
   const Member* m = position_vec3f64(b);
   if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");

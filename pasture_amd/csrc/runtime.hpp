@@ -1,5 +1,6 @@
 // Internal host runtime declarations: device buffers, per-thread workspace, plan execution.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <atomic>
 #include <memory>
@@ -107,6 +108,14 @@ inline const Member* position_vec3f64(const pst_buffer& b) {
   AttributeDef pos{"Position3D", DataType{}};
   pos.datatype.kind = PST_VEC3F64;
   return b.layout.find(pos);
+}
+
+// max_distance of the neighbour searches (nn_api.cpp, hag_api.cpp), checked; returns m2 = max_distance * max_distance, rounded once
+inline double checked_m2(double max_distance, const char* who) {
+  const double m2 = max_distance * max_distance;
+  if (std::isnan(max_distance) || !(max_distance > 0.0) || !(std::isnormal(m2) || std::isinf(m2)))
+    throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": max_distance must be positive (+inf: unbounded), and its square a normal number or +inf");
+  return m2;
 }
 
 // A call's block of device scratch, as a rule carved by a ScratchLayout: allocated on the stream, released in stream order by the destructor
