@@ -729,6 +729,74 @@ int pst_hag_kernel_shape(uint32_t* queries_per_block, uint32_t* max_k, uint32_t*
  * switch.  Host only. */
 int pst_hag_phase_times(double ms[3]);
 
+/* ---- Rasterisation: per-cell statistics of a cloud on an XY grid -------------------------------------------------------------------------
+ * What PDAL's writers.gdal computes before it writes a file (the reference has nothing like it): a surface model (MAX of z), a canopy height
+ * model (MAX of the height above ground), a density image (COUNT), an intensity image (MEAN), and the hole filler every such raster
+ * needs.  Every operation below is a separately rounded f64 operation (no contraction); no square root appears anywhere.  The definitions:
+ *   value:       v_i = the z of point i (d_values == NULL), or d_values[i]: DEVICE memory, len x f64 -- how the d_hag of
+ *                pst_height_above_ground_device is rasterised.  z is not consulted when d_values is given.
+ *   grid:        origin = {x0, y0} and dim = {cols, rows} both given: the caller's grid.  Both NULL: exactly the grid
+ *                pst_pmf_grid(b, cell_size) reports -- over the points with three finite components, WHATEVER d_mask says, so the rasters
+ *                of different masks of one cloud line up cell for cell (a zero origin may differ in its sign).  One without the other, a
+ *                zero in a given dim, an origin that is not finite, a cell_size that is not finite and positive -> PST_ERR_INVALID_ARGUMENT;
+ *                cols * rows > 2^28 -> PST_ERR_UNSUPPORTED.
+ *   cell:        qx = (x - x0) / cell_size, qy = (y - y0) / cell_size.  The point is inside iff qx >= 0.0 && qx < (double)cols &&
+ *                qy >= 0.0 && qy < (double)rows, compared as doubles; then col = (uint32)qx, row = (uint32)qy.  A point exactly at x0 is
+ *                in, one at x0 + cols * cell_size is out, and so is one below x0 by one ulp (a negative quotient).  No finite point is
+ *                outside the automatic grid.
+ *   member:      point i is a member iff x and y are finite, v_i is finite, d_mask is NULL or d_mask[i] != 0 (DEVICE memory, len bytes),
+ *                and the point is inside.
+ *   statistics:  `stats` is a set of PST_RASTER_COUNT (1), PST_RASTER_MIN (2), PST_RASTER_MAX (4), PST_RASTER_MEAN (8) and
+ *                PST_RASTER_VARIANCE (16); 0 or a value above 31 -> PST_ERR_INVALID_ARGUMENT.  out = f64 [planes][rows][cols], one plane per
+ *                set bit in ascending bit order, in device memory (out_memkind = PST_MEM_DEVICE) or host memory (anything else), the
+ *                convention of pst_pmf_ground_mask's surfaces.  Per cell, with its members v_0 .. v_(m-1) in ascending buffer index:
+ *                  COUNT     (double)m
+ *                  MIN, MAX  the member value that is smallest / largest with -0.0 below +0.0; the bits are a member's bits
+ *                  MEAN      S / (double)m, S the CHUNKED sum of the v_t, as is every sum here: chunk j holds the members
+ *                            [256 j, min(m, 256 (j + 1))) (PST_RASTER_CHUNK = 256 is part of this definition), P_j is its left-to-right
+ *                            sum starting from its first element, and S = P_0 + P_1 + ... left to right
+ *                  VARIANCE  SS / (double)m (the population variance): d_t = v_t - MEAN, SS the same chunked sum of the d_t * d_t
+ *                An empty cell has COUNT +0.0 and the canonical quiet NaN (0x7FF8000000000000) in every other plane.  Beyond this, what
+ *                IEEE arithmetic gives is the definition (a sum that overflows, for example).
+ *   results:     *n_members = the sum of the counts; origin_out, dim_out (each optional) = the grid that was used.
+ * The result is a function of the points in buffer order, the values, the mask, the grid and `stats` alone, and two calls write the same
+ * bytes: COUNT, MIN and MAX do not depend on any order, and the sums have the one above.  The chunks exist so that a cell need not be summed
+ * end to end: a request for COUNT, MIN and MAX alone takes one pass of atomics over the positions and no sort; any other sorts the points by
+ * cell with the library's stable radix sort and walks every cell in buffer order, a cell of more than one chunk with a workgroup of its own.
+ * Checks, in the order of pst_pmf_ground_mask: null arguments (b, out, n_members) and invalid parameters are answered before a device is
+ * looked for; then PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64; an empty buffer with the automatic grid is PST_OK on
+ * the host with a zero geometry and nothing written (with a given grid `out` is still filled with the empty-cell values, which needs the
+ * device); then the device (none: PST_ERR_NO_DEVICE, never a CPU path); then 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED.  A buffer
+ * without a finite point and with the automatic grid: a zero geometry, *n_members = 0, `out` untouched.  Out of device memory is
+ * PST_ERR_OUT_OF_MEMORY and the next call works.  Synchronous.  Interleaved or columnar, owned, sliced or external, at any byte offset.
+ * Device scratch: up to 20 bytes per cell on the atomic path; 24 bytes per point and 4 per cell on the sorted one. */
+enum {
+  PST_RASTER_COUNT = 1,
+  PST_RASTER_MIN = 2,
+  PST_RASTER_MAX = 4,
+  PST_RASTER_MEAN = 8,
+  PST_RASTER_VARIANCE = 16,
+  PST_RASTER_CHUNK = 256
+};
+int pst_rasterize(const pst_buffer* b, const double* d_values, const uint8_t* d_mask, double cell_size, const double origin[2], const uint32_t dim[2], uint32_t stats,
+                  double* out, uint32_t out_memkind, double origin_out[2], uint32_t dim_out[2], uint64_t* n_members);
+/* The hole filler (writers.gdal's window_size) of a caller's raster, f64 [rows][cols] in DEVICE memory.  An entry is EMPTY when it is not
+ * finite: the NaN of pst_rasterize and the +inf of the ground filter's surfaces alike.  out[r][c] = in[r][c], the same bits, where the
+ * entry is not empty.  Otherwise the cells (r + dr, c + dc) with |dr| <= half_width and |dc| <= half_width that are inside the raster and
+ * not empty are visited in row-major order (dr ascending, then dc ascending) with w = 1.0 / (double)(dr*dr + dc*dc): the first one sets
+ * num = w*v, den = w, every later one num = num + w*v, den = den + w, and out = num / den -- the canonical NaN if none was visited.
+ * half_width 0 copies the raster bit for bit, its empty entries included.  half_width > 16 -> PST_ERR_INVALID_ARGUMENT (an inverse-distance
+ * fill does not compose from smaller ones).  Stream-ordered; NOT in place (d_in == d_out -> PST_ERR_INVALID_ARGUMENT; the two must not
+ * overlap).  cols * rows > 2^28 -> PST_ERR_UNSUPPORTED; a raster without cells is answered on the host. */
+int pst_grid_fill_device(const double* d_in, double* d_out, uint32_t cols, uint32_t rows, uint32_t half_width);
+/* The kernels' seams (each pointer optional; host only): points per workgroup of the atomic pass, the chunk length of the sums
+ * (PST_RASTER_CHUNK), columns and rows of the raster tile one workgroup of the fill writes, the largest half-width of the fill. */
+int pst_raster_kernel_shape(uint32_t* points_per_block, uint32_t* chunk, uint32_t* fill_tile_cols, uint32_t* fill_tile_rows, uint32_t* fill_max_half_width);
+/* Measurement aid.  With PST_RASTER_TIMES=1 in the environment pst_rasterize brackets its three phases with stream events; this returns the
+ * calling thread's last call: ms = {bounds (zero with a given grid), keys + sort + directory (zero on the atomic path), reduction +
+ * output}.  Zeros without the switch.  Host only. */
+int pst_raster_phase_times(double ms[3]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

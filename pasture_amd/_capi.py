@@ -224,6 +224,10 @@ _PRODUCT_SIGNATURES = {
     "buffer_u8_equals_mask_device": [_P, C.c_char_p, C.c_uint8, _P],
     "hag_kernel_shape": [_U32P, _U32P, _U32P],
     "hag_phase_times": [_D3],
+    "rasterize": [_P, _P, _P, C.c_double, _D3, _U32P, C.c_uint32, _P, C.c_uint32, _D3, _U32P, _U64P],
+    "grid_fill_device": [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32],
+    "raster_kernel_shape": [_U32P, _U32P, _U32P, _U32P, _U32P],
+    "raster_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

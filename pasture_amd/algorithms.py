@@ -905,3 +905,110 @@ def hag_phase_times(api=None):
     ms = (C.c_double * 3)()
     (api or product_api()).hag_phase_times(ms)
     return tuple(ms)
+
+
+# ---- rasterisation: per-cell statistics on an XY grid, and the hole filler (include/pasture_amd.h) --------------------------------------------
+
+RASTER_STATS = {"count": 1, "min": 2, "max": 4, "mean": 8, "variance": 16}  # plane name -> bit of `stats`; the planes come in ascending bit order
+
+
+@dataclass(frozen=True)
+class Raster:
+    """What rasterize returns: the grid that was used -- origin (x0, y0), cell_size, cols, rows; zeros for a cloud without a finite point --,
+    the number of members, and `planes`: statistic name -> float64 (rows, cols) array (empty when the planes went to device memory)."""
+    origin: Tuple[float, float]
+    cell_size: float
+    cols: int
+    rows: int
+    n_members: int
+    planes: dict
+
+
+def _values_column(buffer: _Buffer, attribute: PointAttributeDefinition):
+    """the scalar attribute of every point as a float64 device column (a _DeviceArray), through the layout converter"""
+    from .conversion import BufferLayoutConverter
+    from .layout import PointAttributeDataType as T
+    column = _DeviceArray(buffer.api, T.F64, buffer.len())
+    if buffer.len():
+        converter = BufferLayoutConverter.for_layouts_with_default(buffer.point_layout(), column.buffer.point_layout())
+        converter.set_custom_mapping(attribute, column.attribute)
+        converter.convert_into(buffer, column.buffer)
+    return column
+
+
+def rasterize(buffer: _Buffer, cell_size: float, stats=("max",), values=None, device_mask_ptr: Optional[int] = None, origin=None, dim=None,
+              device_out_ptr: Optional[int] = None) -> Raster:
+    """Per-cell statistics of a cloud on an XY grid, on the device: `stats` names planes of "count", "min", "max", "mean", "variance" and
+    "stdev" (the square root of the variance plane, taken on the host: host results only).  values: None for z, the address of len(buffer)
+    float64 in DEVICE memory (the heights of height_above_ground_device), or a scalar attribute of the buffer (converted to a float64
+    device column).  device_mask_ptr: one byte per point in DEVICE memory, only points with a non-zero byte take part.  origin = (x0, y0)
+    and dim = (cols, rows) together: that grid; neither: pmf_grid's, whatever the mask.  device_out_ptr: the planes go to DEVICE memory
+    there, float64 [planes][rows][cols] in the order count, min, max, mean, variance, and Raster.planes is empty -- the caller sizes it from
+    pmf_grid or the given dim.  An empty cell has count 0 and NaN in every other plane.  (Host planes on the automatic grid cost one
+    pmf_grid call first, to size the arrays.)"""
+    names = [stats] if isinstance(stats, str) else list(stats)
+    unknown = [s for s in names if s not in RASTER_STATS and s != "stdev"]
+    if unknown:
+        raise ValueError(f"unknown statistics {unknown}: choose from {sorted(RASTER_STATS)} and 'stdev'")
+    if device_out_ptr is not None and "stdev" in names:
+        raise ValueError("'stdev' is computed on the host: ask for 'variance' with device_out_ptr")
+    bits = 0
+    for s in names:
+        bits |= RASTER_STATS["variance" if s == "stdev" else s]
+    if (origin is None) != (dim is None):
+        raise ValueError("origin and dim must be given together or not at all")
+    held = None
+    if isinstance(values, PointAttributeDefinition):
+        held = _values_column(buffer, values)
+        values_ptr = held.ptr
+    else:
+        values_ptr = int(values) if values is not None else 0
+    c_origin = (C.c_double * 2)(*origin) if origin is not None else None
+    c_dim = (C.c_uint32 * 2)(*dim) if dim is not None else None
+    origin_out, dim_out, members = (C.c_double * 2)(), (C.c_uint32 * 2)(), C.c_uint64()
+    planes_of = [name for name, bit in RASTER_STATS.items() if bits & bit]
+    host = None
+    if device_out_ptr is None:
+        if dim is not None:
+            cols, rows = int(dim[0]), int(dim[1])
+        else:
+            grid = pmf_grid(buffer, cell_size)
+            cols, rows = grid["cols"], grid["rows"]
+        host = np.full((max(len(planes_of), 1), rows, cols), np.nan, dtype=np.float64)
+        out_ptr, memkind = C.c_void_p(host.ctypes.data if host.size else 1), 1
+    else:
+        out_ptr, memkind = C.c_void_p(int(device_out_ptr) or None), 0
+    buffer.api.rasterize(buffer._h, C.c_void_p(values_ptr or None), C.c_void_p(int(device_mask_ptr or 0) or None), cell_size, c_origin, c_dim, bits, out_ptr, memkind,
+                         origin_out, dim_out, C.byref(members))
+    del held
+    planes = {}
+    if host is not None:
+        by_name = dict(zip(planes_of, host))
+        planes = {s: (np.sqrt(by_name["variance"]) if s == "stdev" else by_name[s]) for s in names}
+    return Raster((origin_out[0], origin_out[1]), cell_size, dim_out[0], dim_out[1], members.value, planes)
+
+
+def grid_fill(device_in_ptr: int, device_out_ptr: int, cols: int, rows: int, half_width: int, api=None) -> None:
+    """Stream-ordered, not in place: the float64 (rows, cols) raster at device_in_ptr with every entry that is not finite (the NaN of
+    rasterize, the +inf of the ground filter's surfaces) replaced by the inverse-squared-distance weighted mean of the finite entries within
+    half_width cells (at most 16) of it, NaN where there is none; finite entries keep their bits."""
+    from ._capi import product_api
+    (api or product_api()).grid_fill_device(C.c_void_p(int(device_in_ptr) or None), C.c_void_p(int(device_out_ptr) or None), cols, rows, half_width)
+
+
+def raster_kernel_shape(api=None) -> dict:
+    """The seams of the rasterisation kernels: points per workgroup of the atomic pass, the chunk length of the sums (part of the definition),
+    columns and rows of a fill tile, the largest fill half-width."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(5)]
+    (api or product_api()).raster_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "chunk", "fill_tile_cols", "fill_tile_rows", "fill_max_half_width"), (x.value for x in v)))
+
+
+def raster_phase_times(api=None):
+    """(bounds, keys + sort + directory, reduction + output) in milliseconds of this thread's last rasterize call; zeros unless
+    PST_RASTER_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).raster_phase_times(ms)
+    return tuple(ms)

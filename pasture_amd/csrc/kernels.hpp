@@ -334,4 +334,41 @@ bool hag_fill_unresolved(const Positions& query, double* hag, double* ground_z, 
 // mask[i] = 1 iff the byte at addr + i * stride equals value, i < n
 bool u8_equals_mask(uint64_t addr, uint64_t stride, uint64_t n, uint8_t value, uint8_t* mask, hipStream_t stream);
 
+// Rasterisation: per-cell statistics of a cloud on an XY grid, and the hole filler (raster.hip; the checks, the grid, the scratch and the order
+// of the launches are in raster_api.cpp).  The seams (pst_raster_kernel_shape):
+constexpr uint32_t kRasterPointsPerBlock = 1024;  // points per workgroup of the atomic pass, four per lane
+constexpr uint32_t kRasterChunk = 256;            // members per chunk of the chunked sums: part of the DEFINITION (include/pasture_amd.h)
+constexpr uint32_t kRasterFillMaxHalfWidth = 16;  // the fill's LDS tile is (kPmfTileRows + 2 h) x (kPmfTileCols + 2 h) doubles: 64 x 96 x 8 = 48 KiB at 16
+constexpr uint32_t kRasterHeavyBlocks = 1024;     // workgroups of the heavy-cell pass at the most; each takes every kRasterHeavyBlocks-th listed cell
+enum : uint32_t { RS_COUNT = 1, RS_MIN = 2, RS_MAX = 4, RS_MEAN = 8, RS_VARIANCE = 16 };
+// what a point's value is and which points take part: values == nullptr: z; mask == nullptr: every point
+struct RasterInput { const double* values; const uint8_t* mask; };
+// the output planes in device memory, rows x cols doubles each; nullptr: not asked for
+struct RasterPlanes { double *count, *min, *max, *mean, *variance; };
+// every plane's empty-cell value (COUNT +0.0, the others the canonical NaN)
+bool raster_fill_empty(const RasterPlanes& out, uint64_t n_cells, hipStream_t stream);
+// The atomic path.  min_keys (every byte 0xFF on entry), max_keys, counts (both zeroed): one per cell, each needed only with its plane;
+// *members (zeroed) += the members, one integer atomic per workgroup
+bool raster_atomic(const Positions& pos, const RasterInput& in, const PmfGrid& g, unsigned long long* min_keys, unsigned long long* max_keys, uint32_t* counts,
+                   unsigned long long* members, hipStream_t stream);
+bool raster_atomic_decode(const unsigned long long* min_keys, const unsigned long long* max_keys, const uint32_t* counts, uint64_t n_cells, const RasterPlanes& out,
+                          hipStream_t stream);
+// The sorted path.  keys[i] = row * cols + col of a member, nonmember_key (a power of two not below cols * rows) of every other point
+bool raster_keys(const Positions& pos, const RasterInput& in, const PmfGrid& g, uint32_t nonmember_key, uint32_t* keys, hipStream_t stream);
+// dir: cols * rows + 1 entries, every byte 0xFF on entry.  dir[cell] = first sorted position of every occupied cell, dir[cols * rows] = the
+// number of members; pstk::suffix_min_u32 over all of it then makes dir[c] the first sorted position whose cell is c or later
+bool raster_directory_heads(const uint32_t* sorted_keys, uint32_t n, uint32_t n_cells, uint32_t* dir, hipStream_t stream);
+// sorted_values[s] = the value of point order[s], s < dir[n_cells]
+bool raster_gather(const Positions& pos, const RasterInput& in, const uint32_t* order, const uint32_t* dir, uint32_t n_cells, double* sorted_values, hipStream_t stream);
+// One lane per cell walks its segment of sorted_values; a cell of more than kRasterChunk members is appended to heavy_list (*heavy_count,
+// zeroed) instead and taken by raster_reduce_heavy, a workgroup per cell; partials: raster_partials_bytes(n) of scratch
+size_t raster_partials_bytes(uint64_t n);
+bool raster_reduce(const double* sorted_values, const uint32_t* dir, uint32_t n_cells, uint32_t stats, const RasterPlanes& out, uint32_t* heavy_list,
+                   uint32_t* heavy_count, hipStream_t stream);
+bool raster_reduce_heavy(const double* sorted_values, const uint32_t* dir, uint32_t n, uint32_t n_cells, uint32_t stats, const RasterPlanes& out, const uint32_t* heavy_list,
+                         const uint32_t* heavy_count, double* partials, hipStream_t stream);
+// The hole filler, out of place: entries that are not finite become the inverse-squared-distance weighted mean of the finite entries of the
+// square of h cells around them (the canonical NaN without one); h <= kRasterFillMaxHalfWidth
+bool raster_grid_fill(const double* in, double* out, uint32_t cols, uint32_t rows, uint32_t h, hipStream_t stream);
+
 }  // namespace pstk

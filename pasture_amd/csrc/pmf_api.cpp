@@ -51,17 +51,8 @@ Schedule make_schedule(const Params& p, const std::string& who) {
 
 // the raster over the finite points' AABB: dim = cell of the largest coordinate + 1, by the expression pmf.hip evaluates per point
 pstk::PmfGrid make_grid(const pstk::ClusterRecord& r, double cell, const std::string& who) {
-  pstk::PmfGrid g{};
-  g.x0 = pstk::cluster_decode_ordered(r.min_ordered[0]);
-  g.y0 = pstk::cluster_decode_ordered(r.min_ordered[1]);
-  g.cell = cell;
-  const double qx = (pstk::cluster_decode_ordered(r.max_ordered[0]) - g.x0) / cell, qy = (pstk::cluster_decode_ordered(r.max_ordered[1]) - g.y0) / cell;
-  // (a quotient that is not below 2^28 -- an extent that overflows f64 included -- is refused before it is converted)
-  const bool fits = qx < (double)kMaxCells && qy < (double)kMaxCells && ((uint64_t)qx + 1) * ((uint64_t)qy + 1) <= kMaxCells;
-  if (!fits) throw Error(PST_ERR_UNSUPPORTED, who + ": the raster would have more than 2^28 cells: use a larger cell_size");
-  g.cols = (uint32_t)qx + 1;
-  g.rows = (uint32_t)qy + 1;
-  return g;
+  return pmf_grid_over(pstk::cluster_decode_ordered(r.min_ordered[0]), pstk::cluster_decode_ordered(r.min_ordered[1]), pstk::cluster_decode_ordered(r.max_ordered[0]),
+                       pstk::cluster_decode_ordered(r.max_ordered[1]), cell, who);
 }
 
 // the AABB record of the finite points, read back (one launch, one synchronisation)

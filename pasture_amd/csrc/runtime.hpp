@@ -118,6 +118,23 @@ inline double checked_m2(double max_distance, const char* who) {
   return m2;
 }
 
+// The raster over an AABB in x and y (pmf_api.cpp, raster_api.cpp): dim = cell of the largest coordinate + 1, by the expression the kernels
+// evaluate per point
+inline pstk::PmfGrid pmf_grid_over(double min_x, double min_y, double max_x, double max_y, double cell, const std::string& who) {
+  constexpr uint64_t kMaxCells = 1ull << 28;
+  pstk::PmfGrid g{};
+  g.x0 = min_x;
+  g.y0 = min_y;
+  g.cell = cell;
+  const double qx = (max_x - g.x0) / cell, qy = (max_y - g.y0) / cell;
+  // (a quotient that is not below 2^28 -- an extent that overflows f64 included -- is refused before it is converted)
+  const bool fits = qx < (double)kMaxCells && qy < (double)kMaxCells && ((uint64_t)qx + 1) * ((uint64_t)qy + 1) <= kMaxCells;
+  if (!fits) throw Error(PST_ERR_UNSUPPORTED, who + ": the raster would have more than 2^28 cells: use a larger cell_size");
+  g.cols = (uint32_t)qx + 1;
+  g.rows = (uint32_t)qy + 1;
+  return g;
+}
+
 // A call's block of device scratch, as a rule carved by a ScratchLayout: allocated on the stream, released in stream order by the destructor
 struct Scratch {
   pstk::DevBuf buf;
