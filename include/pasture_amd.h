@@ -797,6 +797,76 @@ int pst_raster_kernel_shape(uint32_t* points_per_block, uint32_t* chunk, uint32_
  * output}.  Zeros without the switch.  Host only. */
 int pst_raster_phase_times(double ms[3]);
 
+/* ---- Geometric features: the eigenvalues of the neighbourhood covariance and what is derived from them -----------------------------------
+ * What PDAL's filters.covariancefeatures / filters.eigenvalues, CloudCompare's "geometric features" and jakteristics compute (the reference
+ * has none of it): per point the three eigenvalues of the covariance of its k nearest neighbours, linearity, planarity, scattering,
+ * anisotropy, surface variation, omnivariance, eigenentropy, verticality, and the normal, oriented upwards.  Every operation below is a
+ * separately rounded f64 operation; the only exceptions are cbrt and log.  tests/features_ref.py restates the definition in numpy.
+ *   inputs:        Position3D stored as Vec3f64 (interleaved or columnar, owned, sliced or external, at any byte offset); k; neighbour lists
+ *                  uint32 [n][k] in device memory; max_distance (+inf: no limit; a NaN or a negative value -> PST_ERR_INVALID_ARGUMENT); a
+ *                  set of PST_FEATURE_* bits (0 or a value above 8191 -> PST_ERR_INVALID_ARGUMENT).
+ *   neighbourhood: the slots t = 0 .. k-1 of query q are taken in slot order; the lists need not be sorted.  Slot t with index j is VALID
+ *                  iff j < n (the 0xFFFFFFFF padding and any out-of-range index are skipped and never dereferenced), the three coordinates
+ *                  of p_j are finite, and d <= max_distance with d = sqrt((dx*dx + dy*dy) + dz*dz), dx = p_j.x - q.x (y, z alike): the
+ *                  slot distance of pst_knn_search_device.  A query with a coordinate that is not finite has no valid slot.  The query
+ *                  itself counts when its list names it (slot 0 of the library's own lists).  m = the number of valid slots.
+ *   centroid:      each component summed over the valid slots left to right, starting from the first valid one, then / (double)m.
+ *   covariance:    d = p - c; the six sums of d_a * d_b left to right the same way, then / (double)m (the population covariance, as
+ *                  PST_RASTER_VARIANCE is).
+ *   eigen-solve:   scale = the largest absolute value of the six entries.  m < 3, or scale not finite: every requested plane but COUNT, and
+ *                  both vectors, are the canonical quiet NaN (0x7FF8000000000000).  scale == 0: the eigenvalues are +0.0 and V = I.
+ *                  Otherwise A = C / scale entry by entry, V = I, and cyclic Jacobi, at most 10 sweeps.  A sweep first stops the iteration
+ *                  if a01 == 0 && a02 == 0 && a12 == 0; then it visits (p, q) = (0, 1), (0, 2), (1, 2), r the third index:
+ *                    g = |a_pq|; if g != 0 && |a_pp| + g == |a_pp| && |a_qq| + g == |a_qq| then a_pq = 0;  if a_pq == 0: next pair;
+ *                    theta = (a_qq - a_pp) / (2.0 * a_pq);  t = (theta < 0 ? -1.0 : 1.0) / (|theta| + sqrt(theta * theta + 1.0));
+ *                    c = 1.0 / sqrt(t * t + 1.0);  s = t * c;  and from the old values
+ *                    a_pp' = a_pp - t * a_pq, a_qq' = a_qq + t * a_pq, a_pq' = 0, a_rp' = c * a_rp - s * a_rq, a_rq' = s * a_rp + c * a_rq,
+ *                    and for each row i of V: v_ip' = c * v_ip - s * v_iq, v_iq' = s * v_ip + c * v_iq.
+ *                  After the sweeps lambda_i = a_ii * scale; the diagonal is the answer even if the cap was reached.
+ *   order:         the eigenvalues sorted descending, stably (equal values: the lower original index first), each then clamped
+ *                  (lambda > 0 ? lambda : +0.0): l1 >= l2 >= l3 with the eigenvector columns e1, e2, e3 of V.  A vector is negated
+ *                  (unary minus of each component) iff z < 0, or z == 0 && y < 0, or z == 0 && y == 0 && x < 0: normals point up.
+ *   planes:        out = f64 [planes][n] in device memory, one plane per set bit in ascending bit order.  S = (l1 + l2) + l3, e_i = l_i / S:
+ *                    EIGENVALUE_1, _2, _3   l1, l2, l3             SURFACE_VARIATION  l3 / S
+ *                    LINEARITY              (l1 - l2) / l1         EIGENVALUE_SUM     S
+ *                    PLANARITY              (l2 - l3) / l1         VERTICALITY        1.0 - |e3.z|
+ *                    SCATTERING             l3 / l1                OMNIVARIANCE       cbrt((e_1 * e_2) * e_3)
+ *                    ANISOTROPY             (l1 - l3) / l1         EIGENENTROPY       h = 0; for i = 1, 2, 3 with e_i > 0: h = h - e_i * log(e_i)
+ *                    COUNT                  (double)m, always written
+ *                  l1 == 0 (coincident points): the eigenvalue planes and the sum are +0.0; every ratio, verticality, omnivariance, the
+ *                  entropy and both vectors are the canonical NaN, written explicitly.
+ *   vectors:       d_normals f64 [n][3] (e3) and d_directions f64 [n][3] (e1), device memory, each nullable; at least one of d_out,
+ *                  d_normals and d_directions must be given (else PST_ERR_INVALID_ARGUMENT). */
+enum {
+  PST_FEATURE_EIGENVALUE_1 = 1,
+  PST_FEATURE_EIGENVALUE_2 = 2,
+  PST_FEATURE_EIGENVALUE_3 = 4,
+  PST_FEATURE_LINEARITY = 8,
+  PST_FEATURE_PLANARITY = 16,
+  PST_FEATURE_SCATTERING = 32,
+  PST_FEATURE_ANISOTROPY = 64,
+  PST_FEATURE_SURFACE_VARIATION = 128,
+  PST_FEATURE_EIGENVALUE_SUM = 256,
+  PST_FEATURE_VERTICALITY = 512,
+  PST_FEATURE_OMNIVARIANCE = 1024,
+  PST_FEATURE_EIGENENTROPY = 2048,
+  PST_FEATURE_COUNT = 4096,
+  PST_FEATURE_ALL = 8191
+};
+/* The kernel alone, over a caller's lists d_knn (device, uint32 [n][k], required), k = 1 .. 64 (else PST_ERR_INVALID_ARGUMENT).
+ * Stream-ordered on the current stream: no host synchronisation, no allocation.  Checks: null arguments and invalid parameters, then
+ * PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64, all before a device is looked for; an empty buffer is PST_OK on the
+ * host; then the device (none: PST_ERR_NO_DEVICE, never a CPU path); then 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED. */
+int pst_geometric_features_from_knn_device(const pst_buffer* b, size_t k, const uint32_t* d_knn, double max_distance, uint32_t features, double* d_out,
+                                           double* d_normals, double* d_directions);
+/* The search of pst_knn_search_device (the same lists, checks and limits: k = 3 .. 64, at least 3 points, fewer than 2^32 - 16, Vec3f64),
+ * then the kernel above, then a synchronisation.  d_knn (device, nullable): also receive the lists, uint32 [n][k]; scratch otherwise. */
+int pst_geometric_features(const pst_buffer* b, size_t k, double max_distance, uint32_t features, double* d_out, double* d_normals, double* d_directions,
+                           uint32_t* d_knn);
+/* The kernel's seams for this k (tests place their sizes around them; each pointer optional): points whose whole neighbour lists one
+ * workgroup owns, and its threads.  k outside 1 .. 64 -> PST_ERR_INVALID_ARGUMENT.  Host only. */
+int pst_features_kernel_shape(size_t k, uint32_t* points_per_block, uint32_t* threads);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

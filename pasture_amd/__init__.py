@@ -17,6 +17,7 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          cloud_to_cloud_distances, distance_mask, icp, icp_plane, icp_plane_step, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape,
                          PmfParameters, classify_ground, extract_ground, grid_dilate, grid_erode, ground_mask, pmf_grid, pmf_kernel_shape, pmf_phase_times,
                          pmf_schedule, remove_ground, classification_mask, hag_kernel_shape, hag_phase_times, height_above_ground,
-                         height_above_ground_device, normalize_height, Raster, grid_fill, raster_kernel_shape, raster_phase_times, rasterize)
+                         height_above_ground_device, normalize_height, Raster, grid_fill, raster_kernel_shape, raster_phase_times, rasterize,
+                         FEATURES, features_kernel_shape, geometric_features, geometric_features_device)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

@@ -228,6 +228,9 @@ _PRODUCT_SIGNATURES = {
     "grid_fill_device": [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32],
     "raster_kernel_shape": [_U32P, _U32P, _U32P, _U32P, _U32P],
     "raster_phase_times": [_D3],
+    "geometric_features_from_knn_device": [_P, _SZ, _P, C.c_double, C.c_uint32, _P, _P, _P],
+    "geometric_features": [_P, _SZ, C.c_double, C.c_uint32, _P, _P, _P, _P],
+    "features_kernel_shape": [_SZ, _U32P, _U32P],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

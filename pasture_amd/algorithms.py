@@ -1012,3 +1012,82 @@ def raster_phase_times(api=None):
     ms = (C.c_double * 3)()
     (api or product_api()).raster_phase_times(ms)
     return tuple(ms)
+
+
+# ---- geometric features from the eigenvalues of the neighbourhood covariance (include/pasture_amd.h) -----------------------------------------
+
+# plane name -> bit of `features`; the planes come in ascending bit order
+FEATURES = {"eigenvalue_1": 1, "eigenvalue_2": 2, "eigenvalue_3": 4, "linearity": 8, "planarity": 16, "scattering": 32, "anisotropy": 64,
+            "surface_variation": 128, "eigenvalue_sum": 256, "verticality": 512, "omnivariance": 1024, "eigenentropy": 2048, "count": 4096}
+
+
+def _feature_bits(features) -> int:
+    if isinstance(features, (int, np.integer)):
+        return int(features)
+    names = [features] if isinstance(features, str) else list(features)
+    unknown = [s for s in names if s not in FEATURES]
+    if unknown:
+        raise ValueError(f"unknown features {unknown}: choose from {list(FEATURES)}")
+    bits = 0
+    for s in names:
+        bits |= FEATURES[s]
+    return bits
+
+
+def geometric_features_device(buffer: _Buffer, k: int, features, out_ptr: int, max_distance: float = float("inf"), normals_ptr: int = 0, directions_ptr: int = 0,
+                              knn_ptr: int = 0, from_knn: bool = False) -> None:
+    """Per-point features of the covariance of the k nearest neighbours, everything in caller-owned DEVICE memory: out_ptr float64 [planes][n],
+    one plane per feature (names of FEATURES, or their bits) in ascending bit order; normals_ptr / directions_ptr float64 [n][3], the
+    eigenvectors of the smallest / largest eigenvalue, oriented upwards; 0 = not wanted, but one of the three is needed.  knn_ptr: uint32
+    [n][k].  from_knn=False: the library searches (k = 3 .. 64) and, if knn_ptr is given, leaves its lists there; synchronous.
+    from_knn=True: the lists at knn_ptr are the input (k = 1 .. 64; indices >= n are skipped); stream-ordered, no synchronisation.
+    Only neighbours within max_distance of the query take part."""
+    p = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
+    if from_knn:
+        buffer.api.geometric_features_from_knn_device(buffer._h, k, p(knn_ptr), max_distance, _feature_bits(features), p(out_ptr), p(normals_ptr), p(directions_ptr))
+    else:
+        buffer.api.geometric_features(buffer._h, k, max_distance, _feature_bits(features), p(out_ptr), p(normals_ptr), p(directions_ptr), p(knn_ptr))
+
+
+def geometric_features(buffer: _Buffer, k: int, features=("linearity", "planarity", "scattering", "verticality"), max_distance: float = float("inf"), knn=None,
+                       return_normals: bool = False, return_directions: bool = False) -> dict:
+    """PDAL's filters.covariancefeatures / CloudCompare's geometric features on the device: a dict from feature name (FEATURES) to a float64
+    (n,) array, with "normals" / "directions" (n, 3) when asked for.  knn: an optional (n, k) integer array of neighbour indices (-1 or
+    anything >= n: no neighbour), as knn_search returns it; without it the library searches the k nearest neighbours itself.  A point with
+    fewer than 3 valid neighbours has NaN everywhere but in "count"."""
+    from .layout import PointAttributeDataType as T
+    names = [features] if isinstance(features, str) else list(features)
+    bits = _feature_bits(names)
+    planes_of = [name for name, bit in FEATURES.items() if bits & bit]
+    n = buffer.len()
+    lists = None
+    if knn is not None:
+        knn = np.asarray(knn)
+        if knn.ndim != 2 or knn.shape != (n, k) or knn.dtype.kind not in "iu":
+            raise ValueError("knn must be an integer array of shape (len(buffer), k)")
+        lists = _DeviceArray(buffer.api, T.U32, n * k)
+        if n * k:
+            lists.buffer.set_attribute_range(lists.attribute, range(0, n * k), (knn.astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32))
+    out = _DeviceArray(buffer.api, T.F64, n * len(planes_of))
+    normals = _DeviceArray(buffer.api, T.F64, n * 3) if return_normals else None
+    directions = _DeviceArray(buffer.api, T.F64, n * 3) if return_directions else None
+    # (an empty array has no address: the calls' own checks answer such a buffer before anything is dereferenced)
+    geometric_features_device(buffer, k, bits, out.ptr or (1 if planes_of else 0), max_distance, (normals.ptr or 1) if normals else 0,
+                              (directions.ptr or 1) if directions else 0, (lists.ptr or 1) if lists else 0, from_knn=lists is not None)
+    if lists is not None:
+        buffer.api.stream_synchronize()
+    result = dict(zip(planes_of, out.to_numpy().reshape(len(planes_of), n)))
+    result = {s: result[s] for s in names}
+    if normals:
+        result["normals"] = normals.to_numpy().reshape(n, 3)
+    if directions:
+        result["directions"] = directions.to_numpy().reshape(n, 3)
+    return result
+
+
+def features_kernel_shape(k: int, api=None) -> dict:
+    """The seams of the feature kernel at this k: points whose whole neighbour lists one workgroup owns, and its threads."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).features_kernel_shape(k, *[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "threads"), (x.value for x in v)))

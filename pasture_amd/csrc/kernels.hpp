@@ -212,6 +212,13 @@ bool outlier_statistics_and_mask(const double* dbar_dev, uint64_t n, double stdd
 bool outlier_radius_mask(const Positions& pos, uint32_t k, uint32_t slot, double radius, const uint32_t* knn_dev, void* record, uint8_t* mask_dev,
                          hipStream_t stream);
 
+// Geometric features over the kNN lists (features.hip).  The kernel's seams (pst_features_kernel_shape):
+constexpr uint32_t kFeaturesThreads = 256;         // threads of a workgroup
+uint32_t features_points_per_block(uint32_t k);    // points whose whole lists one workgroup stages in LDS: 256, 128, 64, 32 for k <= 8, 16, 32, 64
+// knn_dev: uint32 [n][k]; out_dev: f64 [planes][n], one plane per bit of `features`; normals_dev, directions_dev: f64 [n][3]; each output nullable
+bool geometric_features(const Positions& pos, uint32_t k, const uint32_t* knn_dev, double max_distance, uint32_t features, double* out_dev, double* normals_dev,
+                        double* directions_dev, hipStream_t stream);
+
 // Euclidean cluster extraction (clusters.hip; the pipeline and its scratch are laid out in clusters_api.cpp).  The seams (pst_cluster_kernel_shape):
 constexpr uint32_t kClusterPointsPerBlock = 256;  // points one workgroup of the traversal kernel owns, one lane each
 constexpr uint32_t kClusterTilePoints = 0;        // points of an LDS candidate tile: none, the candidates are read from the sorted arrays

@@ -3,33 +3,11 @@
 #include <cmath>
 
 #include "device_sort.hpp"
-#include "runtime.hpp"
+#include "knn_checks.hpp"
 
 using namespace pst;
 
 namespace {
-
-// The checks of pst_compute_normals_device in two halves: what the arguments and the layout alone decide is answered before a device is looked
-// for, the cloud's length after it (so a call without a device is PST_ERR_NO_DEVICE whatever the buffer holds).
-const Member& checked_arguments(const pst_buffer& b, size_t k, const char* who) {
-  if (k < 3) throw Error(PST_ERR_K_TOO_SMALL, "The k nearest neigbors attribute is too small!");
-  if (k > 64) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": k > 64 is not supported by the register-resident k-best list");
-  const Member* m = position_vec3f64(b);
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
-  return *m;
-}
-void checked_length(const pst_buffer& b, size_t at_least, const char* who) {
-  if (b.len < 3) throw Error(PST_ERR_TOO_FEW_POINTS, "The point cloud is too small. Please use a point cloud that has 3 or more points!");
-  if (b.len < at_least) throw Error(PST_ERR_TOO_FEW_POINTS, std::string(who) + ": the point cloud needs at least " + std::to_string(at_least) + " points");
-  if (b.len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
-}
-
-// the neighbour lists only; degenerate plane fits (a positive return) are no error here: the lists are written whatever the fit says
-void search(const pstk::Positions& pv, size_t k, uint32_t* d_knn, hipStream_t s, const char* who) {
-  const long long rc = pstk::run_normals(pv.base, pv.stride, pv.n, (uint32_t)k, nullptr, nullptr, nullptr, d_knn, 0, 0, 0, 0, s);
-  if (rc == -2) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
-  if (rc < 0) throw hip_failure(std::string(who) + ": neighbour search failed: ");
-}
 
 void check_mask_args(const uint8_t* mask, uint32_t mask_memkind, const uint64_t* kept) {
   not_null(mask, "mask");
@@ -55,14 +33,14 @@ int pst_knn_search_device(const pst_buffer* b, size_t k, uint32_t* d_knn, double
   const char* who = "pst_knn_search_device";
   not_null(b, "buffer");
   not_null(d_dist, "d_dist");
-  const Member& pm = checked_arguments(*b, k, who);
+  const Member& pm = knn_checked_arguments(*b, k, who);
   ensure_device();
-  checked_length(*b, 3, who);
+  knn_checked_length(*b, 3, who);
   hipStream_t s = current_stream();
   const pstk::Positions pv = positions_of(*b, pm);
   Scratch own;
   if (!d_knn) d_knn = own.alloc<uint32_t>(pv.n * k * sizeof(uint32_t), s, who);
-  search(pv, k, d_knn, s, who);
+  knn_lists(pv, k, d_knn, s, who);
   if (!pstk::outlier_distances(pv, (uint32_t)k, d_knn, d_dist, s)) throw hip_failure("knn_search: distance launch failed: ");
   stream_sync(s);
   PST_API_END
@@ -78,9 +56,9 @@ int pst_statistical_outlier_mask(const pst_buffer* b, size_t mean_k, double stdd
   if (mean_k < 1 || mean_k > 63) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": mean_k must be between 1 and 63");
   if (std::isnan(stddev_mult)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": stddev_mult is NaN");
   const size_t k = std::max<size_t>(mean_k + 1, 3);
-  const Member& pm = checked_arguments(*b, k, who);
+  const Member& pm = knn_checked_arguments(*b, k, who);
   ensure_device();
-  checked_length(*b, mean_k + 1, who);
+  knn_checked_length(*b, mean_k + 1, who);
   hipStream_t s = current_stream();
   const pstk::Positions pv = positions_of(*b, pm);
   const size_t n = pv.n;
@@ -95,7 +73,7 @@ int pst_statistical_outlier_mask(const pst_buffer* b, size_t mean_k, double stdd
   double* dbar = d_mean_dist ? d_mean_dist : scratch.at<double>(off_dbar);
   void* rec = scratch.at<void>(off_rec);
   uint8_t* mask_dev = mask_on_device ? mask : scratch.at<uint8_t>(off_mask);
-  search(pv, k, d_knn, s, who);
+  knn_lists(pv, k, d_knn, s, who);
   if (!pstk::outlier_mean_distances(pv, (uint32_t)k, (uint32_t)mean_k, d_knn, dbar, s) ||
       !pstk::outlier_statistics_and_mask(dbar, n, stddev_mult, scratch.at<void>(off_part), rec, mask_dev, s))
     throw hip_failure("statistical outlier launch failed: ");
@@ -116,9 +94,9 @@ int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neigh
   if (min_neighbours < 1 || min_neighbours > 63) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": min_neighbours must be between 1 and 63");
   if (!(radius >= 0.0) || std::isinf(radius)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": radius must be finite and not negative");
   const size_t k = std::max<size_t>(min_neighbours + 1, 3);
-  const Member& pm = checked_arguments(*b, k, who);
+  const Member& pm = knn_checked_arguments(*b, k, who);
   ensure_device();
-  checked_length(*b, 3, who);
+  knn_checked_length(*b, 3, who);
   hipStream_t s = current_stream();
   const pstk::Positions pv = positions_of(*b, pm);
   const size_t n = pv.n;
@@ -129,7 +107,7 @@ int pst_radius_outlier_mask(const pst_buffer* b, double radius, size_t min_neigh
   uint32_t* d_knn = scratch.at<uint32_t>(off_knn);
   void* rec = scratch.at<void>(off_rec);
   uint8_t* mask_dev = mask_on_device ? mask : scratch.at<uint8_t>(off_mask);
-  search(pv, k, d_knn, s, who);
+  knn_lists(pv, k, d_knn, s, who);
   if (!pstk::outlier_radius_mask(pv, (uint32_t)k, (uint32_t)min_neighbours, radius, d_knn, rec, mask_dev, s)) throw hip_failure("radius outlier launch failed: ");
   HostRecord r{};
   PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
