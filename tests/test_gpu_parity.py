@@ -9,7 +9,7 @@ from pasture_amd import las
 from pasture_amd._capi import PastureError, PasturePanic
 from pasture_amd.algorithms import calculate_bounds, transform_attribute
 from pasture_amd.buffers import HashMapBuffer, VectorBuffer
-from pasture_amd.conversion import BufferLayoutConverter, Transform
+from pasture_amd.conversion import BufferLayoutConverter, Transform, last_plan_kinds
 from pasture_amd.layout import PointAttributeDataType as T, PointAttributeDefinition, PointLayout, attributes as A
 
 pytestmark = pytest.mark.gpu
@@ -48,6 +48,7 @@ def test_synth_matches_oracle(hip, oracle, kind, packed):
 def test_raw_las_to_typed_layout_vs_oracle(hip, oracle, fmt, target_kind):
     """The production caller (raw_readers.rs:299-352) on 200k synthetic raw records per format, written in two ranges."""
     n = 200_003
+    kinds = []  # the kernel families the HIP calls took (tests/test_las_seams.py pins each family; here: which one this comparison covered)
 
     def run(api):
         raw = las.point_layout_from_las_point_format(las.Format(fmt), True, api=api)
@@ -60,11 +61,16 @@ def test_raw_las_to_typed_layout_vs_oracle(hip, oracle, fmt, target_kind):
         out.resize(n)
         cut = 77_777
         conv.convert_into_range(src, range(0, cut), out, range(0, cut))
+        if api is hip:
+            kinds.append(last_plan_kinds(hip))
         conv.convert_into_range(src, range(cut, n), out, range(cut, n))
+        if api is hip:
+            kinds.append(last_plan_kinds(hip))
         return out.get_point_range(range(0, n)), calculate_bounds(out)
     (hp, hb), (op, ob) = both(run, hip, oracle)
-    assert hp.tobytes() == op.tobytes()
-    assert hb == ob
+    assert len(kinds) == 2 and all(k and "none" not in k for k in kinds), kinds
+    assert hp.tobytes() == op.tobytes(), kinds
+    assert hb == ob, kinds
 
 
 @pytest.mark.parametrize("pair", PAIRINGS)
@@ -1862,6 +1868,7 @@ def test_typed_las_storage_transposition_vs_oracle(hip, oracle, fmt, pair):
     """BufferLayoutConverter::for_layouts(L, L) between a VectorBuffer and a HashMapBuffer of LasPointFormatN::layout()
     (configs[2] is V -> H for format 0): the format-specialised transposition, in two ragged ranges with offsets."""
     n, cut, pad = 150_003, 40_001, 3
+    kinds = []  # the kernel families the HIP calls took
 
     def run(api):
         layout = las.point_layout_from_las_point_format(las.Format(fmt), False, api=api)
@@ -1872,10 +1879,15 @@ def test_typed_las_storage_transposition_vs_oracle(hip, oracle, fmt, pair):
         dst.resize(n + pad)
         conv = BufferLayoutConverter.for_layouts(layout, layout)
         conv.convert_into_range(src, range(0, cut), dst, range(pad, pad + cut))
+        if api is hip:
+            kinds.append(last_plan_kinds(hip))
         conv.convert_into_range(src, range(cut, n), dst, range(pad + cut, pad + n))
+        if api is hip:
+            kinds.append(last_plan_kinds(hip))
         return dst.get_point_range(range(0, n + pad)).tobytes()
     h, o = both(run, hip, oracle)
-    assert h == o
+    assert len(kinds) == 2 and all(k and "none" not in k for k in kinds), kinds
+    assert h == o, kinds
 
 
 _STRIDE_LAYOUTS = {

@@ -10,6 +10,7 @@ import pytest
 
 import las_expected as E
 from harness import BUFFER_KINDS
+from las_ref import numpy_encode  # the independent numpy restatement (positions in range)
 from pasture_amd import las
 from pasture_amd._capi import PasturePanic
 from pasture_amd.buffers import HashMapBuffer, VectorBuffer
@@ -61,39 +62,6 @@ def layouts(fmt, api):
 def raw_bytes(buf) -> np.ndarray:
     n = buf.len()
     return np.ascontiguousarray(buf.get_point_range(range(0, n))).view(np.uint8).reshape(n, -1)
-
-
-def numpy_encode(rec, fmt, scale, offset) -> np.ndarray:
-    """Independent numpy restatement used to cross-check oracle and HIP on random data (positions assumed in range)."""
-    F = las.Format(fmt)
-    n = len(rec)
-    parts = []
-    local = (rec[A.POSITION_3D.name()] - np.asarray(offset)) / np.asarray(scale)
-    parts.append(np.trunc(local).astype(np.int64).astype("<i4").view(np.uint8).reshape(n, 12))
-    parts.append(rec[A.INTENSITY.name()].astype("<u2").view(np.uint8).reshape(n, 2))
-    rn, nr = rec[A.RETURN_NUMBER.name()], rec[A.NUMBER_OF_RETURNS.name()]
-    sd, eof = rec[A.SCAN_DIRECTION_FLAG.name()], rec[A.EDGE_OF_FLIGHT_LINE.name()]
-    if F.is_extended:
-        cf, sc = rec[A.CLASSIFICATION_FLAGS.name()], rec[A.SCANNER_CHANNEL.name()]
-        parts.append(((rn & 15) | ((nr & 15) << 4)).astype(np.uint8).reshape(n, 1))
-        parts.append(((cf & 15) | ((sc & 3) << 4) | ((sd & 1) << 6) | ((eof & 1) << 7)).astype(np.uint8).reshape(n, 1))
-    else:
-        parts.append(((rn & 7) | ((nr & 7) << 3) | ((sd & 1) << 6) | ((eof & 1) << 7)).astype(np.uint8).reshape(n, 1))
-    parts.append(rec[A.CLASSIFICATION.name()].reshape(n, 1))
-    if F.is_extended:
-        parts.append(rec[A.USER_DATA.name()].reshape(n, 1))
-        parts.append(rec[A.SCAN_ANGLE.name()].astype("<i2").view(np.uint8).reshape(n, 2))
-    else:
-        parts.append(rec[A.SCAN_ANGLE_RANK.name()].view(np.uint8).reshape(n, 1))
-        parts.append(rec[A.USER_DATA.name()].reshape(n, 1))
-    parts.append(rec[A.POINT_SOURCE_ID.name()].astype("<u2").view(np.uint8).reshape(n, 2))
-    tail = [(F.has_gps_time, A.GPS_TIME), (F.has_color, A.COLOR_RGB), (F.has_nir, A.NIR), (F.has_waveform, A.WAVE_PACKET_DESCRIPTOR_INDEX),
-            (F.has_waveform, A.WAVEFORM_DATA_OFFSET), (F.has_waveform, A.WAVEFORM_PACKET_SIZE), (F.has_waveform, A.RETURN_POINT_WAVEFORM_LOCATION),
-            (F.has_waveform, A.WAVEFORM_PARAMETERS)]
-    for present, attr in tail:
-        if present:
-            parts.append(np.ascontiguousarray(rec[attr.name()]).view(np.uint8).reshape(n, -1))
-    return np.concatenate(parts, axis=1)
 
 
 def random_typed(layout, n, seed):
