@@ -500,6 +500,50 @@ int pst_cluster_kernel_shape(uint32_t* points_per_block, uint32_t* tile_points);
  * switch.  Host only. */
 int pst_cluster_phase_times(double ms[3]);
 
+/* ---- Minimum-distance (Poisson-disk) subsampling ----------------------------------------------------------------------------------------
+ * What PDAL's filters.sample, CloudCompare's "subsample by space" and lidR's decimate_points compute (the reference has none of them): a
+ * subset of the ORIGINAL points in which no two are closer than a radius, as a byte mask that pst_buffer_filter / pst_buffer_filter_into
+ * take -- unlike pst_voxelgrid_filter, which invents centroids and guarantees no spacing.  The definition:
+ *   finite point:  as for the clusters.  A point with a NaN or +-inf coordinate is never kept and conflicts with nothing.
+ *   conflict:      finite points i and j conflict iff (dx*dx + dy*dy) + dz*dz <= r2, dx = pj.x - pi.x (y, z alike), every operation a
+ *                  separately rounded f64 operation, r2 = radius * radius rounded once on the host.  There is no sqrt.  This is the
+ *                  adjacency of pst_euclidean_clusters, on purpose: a thinned cloud clustered at tolerance = radius is all singletons.
+ *   priority key:  a uint64 per buffer index i.  PST_SAMPLE_SHUFFLED (0): splitmix64(seed ^ i), the finaliser written out at
+ *                  pst_ransac_sample_indices -- a bijection on 64 bits, so keys never tie.  PST_SAMPLE_INDEX_ORDER (1): i itself, the seed
+ *                  is ignored -- PDAL's filters.sample exactly: the first point is always kept.
+ *   kept set:      finite i is kept iff no kept j with a smaller key conflicts with it -- the result of the sequential greedy pass in
+ *                  ascending key order.  It is unique and depends on nothing else: not on the grid, the schedule, the storage or the number
+ *                  of rounds.
+ *   mask:          mask[i] = 1 kept, 0 otherwise.
+ * Two calls on one cloud write the same bytes.
+ * Null arguments, an invalid memory kind, an order above 1, a radius not finite, not > 0 or with radius * radius not a normal number ->
+ * PST_ERR_INVALID_ARGUMENT, answered before a device is looked for; then Position3D not stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE
+ * (interleaved or columnar, owned, sliced or external, at any byte offset); then the device: without one the call is PST_ERR_NO_DEVICE, never a
+ * CPU path; then the length: 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED (so is a cloud whose finite extent overflows f64).  Any length
+ * from 0 up is legal: an empty cloud keeps nothing (answered on the host, *kept = 0, *rounds = 0); a cloud without a finite point gets an
+ * all-zero mask and 0 rounds.
+ * Cost: the index build of pst_euclidean_clusters, then rounds.  In a round every still undecided point tests the points of its own and the
+ * 26 neighbouring grid cells (cell edge just above the radius) -- a radius far above the point spacing is quadratic per cell, as for the
+ * clusters -- and decides when every conflicting point of smaller key has decided.  Shuffled keys need about ten rounds whatever the input
+ * order.  PST_SAMPLE_INDEX_ORDER is correct but SLOW on ordered input: along a scan line every point waits for its predecessor, so the
+ * number of rounds grows with the length of the chains of conflicts (hundreds of rounds on scan-line ordered LiDAR). */
+#define PST_SAMPLE_SHUFFLED 0u
+#define PST_SAMPLE_INDEX_ORDER 1u
+/* Synchronous.  mask: len bytes in device memory (mask_memkind = PST_MEM_DEVICE) or host memory (anything else), the convention of the
+ * outlier masks.  *kept = the number of ones.  rounds (nullable): *rounds = launches of the decision kernel. */
+int pst_poisson_disk_mask(const pst_buffer* b, double radius, uint32_t order, uint64_t seed, uint8_t* mask, uint32_t mask_memkind, uint64_t* kept,
+                          uint32_t* rounds);
+/* Host only, no device needed: keys[j] = the priority key of buffer index first + j, j < count (the keys of the definition above; first + j
+ * wraps at 2^64).  count == 0 writes nothing; an order above 1 -> PST_ERR_INVALID_ARGUMENT. */
+int pst_sample_priorities(uint32_t order, uint64_t seed, uint64_t first, uint64_t count, uint64_t* keys);
+/* The decision kernel's seams (tests place their sizes around them; each pointer optional): active points one workgroup owns (one lane each),
+ * times a lane looks at its point in one launch before it leaves it undecided.  Host only. */
+int pst_sample_kernel_shape(uint32_t* points_per_block, uint32_t* sweeps_per_launch);
+/* Measurement aid.  With PST_SAMPLE_TIMES=1 in the environment pst_poisson_disk_mask brackets its three phases with stream events; this
+ * returns the calling thread's last call: ms = {index build (AABB, keys, sort, gather), decision rounds, mask write}.  Zeros without the
+ * switch.  Host only. */
+int pst_sample_phase_times(double ms[3]);
+
 /* ---- Ground classification (progressive morphological filter) ------------------------------------------------------------------------
  * What PDAL's filters.pmf and PCL's ProgressiveMorphologicalFilter compute (Zhang et al. 2003; the reference has neither), with square
  * windows: the points are rasterised to their lowest z per cell, the raster is opened (eroded, then dilated) with growing windows, and a

@@ -18,6 +18,7 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          PmfParameters, classify_ground, extract_ground, grid_dilate, grid_erode, ground_mask, pmf_grid, pmf_kernel_shape, pmf_phase_times,
                          pmf_schedule, remove_ground, classification_mask, hag_kernel_shape, hag_phase_times, height_above_ground,
                          height_above_ground_device, normalize_height, Raster, grid_fill, raster_kernel_shape, raster_phase_times, rasterize,
-                         FEATURES, features_kernel_shape, geometric_features, geometric_features_device)
+                         FEATURES, features_kernel_shape, geometric_features, geometric_features_device,
+                         poisson_disk_mask, sample_kernel_shape, sample_phase_times, sample_priorities, subsample_min_distance)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

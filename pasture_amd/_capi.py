@@ -231,6 +231,10 @@ _PRODUCT_SIGNATURES = {
     "geometric_features_from_knn_device": [_P, _SZ, _P, C.c_double, C.c_uint32, _P, _P, _P],
     "geometric_features": [_P, _SZ, C.c_double, C.c_uint32, _P, _P, _P, _P],
     "features_kernel_shape": [_SZ, _U32P, _U32P],
+    "poisson_disk_mask": [_P, C.c_double, C.c_uint32, C.c_uint64, _P, C.c_uint32, _U64P, _U32P],
+    "sample_priorities": [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _U64P],
+    "sample_kernel_shape": [_U32P, _U32P],
+    "sample_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -1091,3 +1091,59 @@ def features_kernel_shape(k: int, api=None) -> dict:
     v = [C.c_uint32() for _ in range(2)]
     (api or product_api()).features_kernel_shape(k, *[C.byref(x) for x in v])
     return dict(zip(("points_per_block", "threads"), (x.value for x in v)))
+
+
+# ---- minimum-distance (Poisson-disk) subsampling (include/pasture_amd.h) ---------------------------------------------------------------------
+
+SAMPLE_ORDERS = {"shuffled": 0, "index": 1}
+
+
+def _sample_order(order) -> int:
+    if order not in SAMPLE_ORDERS:
+        raise ValueError(f"order must be one of {sorted(SAMPLE_ORDERS)}")
+    return SAMPLE_ORDERS[order]
+
+
+def sample_priorities(order, seed: int, first: int, count: int, api=None) -> np.ndarray:
+    """The priority keys of buffer indices first .. first + count - 1 (host only): splitmix64(seed ^ i) for "shuffled", i for "index"."""
+    from ._capi import product_api
+    keys = np.zeros(count, dtype=np.uint64)
+    (api or product_api()).sample_priorities(_sample_order(order), seed & 0xFFFFFFFFFFFFFFFF, first & 0xFFFFFFFFFFFFFFFF, count, _u64(keys) if count else None)
+    return keys
+
+
+def poisson_disk_mask(buffer: _Buffer, radius: float, seed: int = 0, order: str = "shuffled", device_mask_ptr: Optional[int] = None):
+    """PDAL's filters.sample / CloudCompare's "subsample by space" on the device: the greedy pass in ascending priority key that keeps a finite
+    point iff no kept point lies within `radius` of it.  order "shuffled": keys splitmix64(seed ^ index); "index": the buffer order itself
+    (the first point is always kept; slow on scan-line ordered clouds).  Returns (mask, kept, rounds): mask is a numpy uint8 array (1 = keep),
+    or None when the bytes went to DEVICE memory at device_mask_ptr -- what filter takes as (ptr, 'device'); rounds = launches of the decision
+    kernel."""
+    n = buffer.len()
+    kept, rounds = C.c_uint64(), C.c_uint32()
+    mask = np.zeros(n, dtype=np.uint8) if device_mask_ptr is None else None
+    ptr = C.c_void_p(int(device_mask_ptr) or None) if mask is None else C.c_void_p(mask.ctypes.data if n else 1)
+    buffer.api.poisson_disk_mask(buffer._h, radius, _sample_order(order), seed & 0xFFFFFFFFFFFFFFFF, ptr, 0 if mask is None else 1, C.byref(kept), C.byref(rounds))
+    return mask, kept.value, rounds.value
+
+
+def subsample_min_distance(buffer: _Buffer, radius: float, seed: int = 0, order: str = "shuffled", out_buffer_type=None):
+    """(the points poisson_disk_mask keeps, in buffer order with all their attributes; their number): mask and compaction stay in device
+    memory.  `buffer` is columnar (filter is defined on HashMapBuffer)."""
+    return _filter_by_device_mask(buffer, out_buffer_type, lambda p: poisson_disk_mask(buffer, radius, seed, order, device_mask_ptr=p or 1)[1])
+
+
+def sample_kernel_shape(api=None) -> dict:
+    """The seams of the decision kernel: active points one workgroup owns, sweeps of a lane over its point per launch."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).sample_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "sweeps_per_launch"), (x.value for x in v)))
+
+
+def sample_phase_times(api=None):
+    """(index build, decision rounds, mask write) in milliseconds of this thread's last poisson_disk_mask call; zeros unless
+    PST_SAMPLE_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).sample_phase_times(ms)
+    return tuple(ms)

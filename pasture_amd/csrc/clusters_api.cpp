@@ -11,34 +11,6 @@ using namespace pst;
 
 namespace {
 
-constexpr uint32_t kMaxCellsPerAxis = (1u << 21) - 1;  // 21 key bits per axis: 63 in all, and one more bit tells the all-ones key apart
-
-uint32_t bits_for(uint32_t cells) {  // key bits that hold the cell numbers 0 .. cells - 1
-  uint32_t b = 0;
-  while ((1ull << b) < cells) ++b;
-  return b;
-}
-
-// The uniform grid over the finite points' AABB.  The edge is the tolerance times (1 + 2^-20) -- STRICTLY larger, by far more than any rounding
-// of the cell numbers (the argument is at the head of clusters.hip) -- and is doubled until no axis needs more than 2^21 - 1 cells: coarser cells
-// cost pair tests, never exactness.  dim = cell of the largest coordinate + 1, by the expression the key kernel evaluates per point.
-pstk::ClusterGrid make_grid(const pstk::ClusterRecord& r, double tolerance) {
-  pstk::ClusterGrid g{};
-  double extent[3];
-  for (int a = 0; a < 3; ++a) {
-    g.min[a] = pstk::cluster_decode_ordered(r.min_ordered[a]);
-    extent[a] = pstk::cluster_decode_ordered(r.max_ordered[a]) - g.min[a];
-    if (!std::isfinite(extent[a])) throw Error(PST_ERR_UNSUPPORTED, "pst_euclidean_clusters: the extent of the finite points overflows f64");
-  }
-  g.edge = tolerance * (1.0 + 0x1p-20);
-  while (extent[0] / g.edge >= (double)kMaxCellsPerAxis || extent[1] / g.edge >= (double)kMaxCellsPerAxis || extent[2] / g.edge >= (double)kMaxCellsPerAxis) g.edge *= 2.0;
-  for (int a = 0; a < 3; ++a) {
-    g.dim[a] = (uint32_t)(extent[a] / g.edge) + 1;
-    g.bits[a] = bits_for(g.dim[a]);
-  }
-  return g;
-}
-
 thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
 
 // PST_CLUSTER_TIMES=1: stream events around the three phases of every call (tools/bench_clusters.py reads them through pst_cluster_phase_times)
@@ -166,7 +138,12 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
     stream_sync(s);
     return PST_OK;
   }
-  const pstk::ClusterGrid grid = make_grid(r, tolerance);
+  double lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = pstk::cluster_decode_ordered(r.min_ordered[a]);
+    hi[a] = pstk::cluster_decode_ordered(r.max_ordered[a]);
+  }
+  const pstk::ClusterGrid grid = cluster_grid_over(lo, hi, tolerance, who);
   const unsigned key_bits = grid.bits[0] + grid.bits[1] + grid.bits[2];
   if (!pstk::cluster_keys(pos, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure("cluster key launch failed: ");
   size_t bytes = tmp_bytes;

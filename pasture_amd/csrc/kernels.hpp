@@ -378,4 +378,24 @@ bool raster_reduce_heavy(const double* sorted_values, const uint32_t* dir, uint3
 // square of h cells around them (the canonical NaN without one); h <= kRasterFillMaxHalfWidth
 bool raster_grid_fill(const double* in, double* out, uint32_t cols, uint32_t rows, uint32_t h, hipStream_t stream);
 
+// Minimum-distance (Poisson-disk) subsampling (sample.hip; the checks, the scratch and the loop of rounds are in sample_api.cpp).  The index is
+// the cluster index: cluster_keys on a ClusterGrid, the 64-bit sort, nn_gather.  The seams (pst_sample_kernel_shape):
+constexpr uint32_t kSamplePointsPerBlock = 256;         // active points one workgroup of the decision kernel owns, one lane each
+constexpr uint32_t kSampleSweepsPerLaunch = 2;          // times a lane looks at its point in one launch before it leaves it undecided
+constexpr uint32_t kSampleBoundsPointsPerBlock = 4096;  // points per block partial of the bounds, sixteen per lane
+// the device-side record of the bounds: the AABB of the finite points and their number ({+inf .., -inf .., 0} without one)
+struct SampleBounds { double min[3], max[3]; unsigned long long count; };
+size_t sample_bounds_partials_bytes(uint64_t n);
+// block partials, then one workgroup folds them into *rec; no atomics
+bool sample_bounds(const Positions& pos, void* partials, SampleBounds* rec, hipStream_t stream);
+// One launch of the decision kernel over the m active points (active == nullptr: the sorted points 0 .. m - 1, m == nf).  state: one byte per
+// sorted point, 0 undecided (what the caller sets before the first round), 1 kept, 2 rejected.  flags: m + 1 entries, flags[t] = 1 iff active
+// point t is still undecided afterwards, flags[m] = 0.  shuffled != 0: priority key splitmix64(seed ^ index), else the index.
+bool sample_decide(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, const uint32_t* order, uint32_t nf, const ClusterGrid& g,
+                   double r2, uint32_t shuffled, uint64_t seed, const uint32_t* active, uint32_t m, uint8_t* state, uint32_t* flags, hipStream_t stream);
+// offsets = exclusive sum of flags: next[offsets[t]] = active point t for every flagged t
+bool sample_compact(const uint32_t* active, const uint32_t* flags, const unsigned long long* offsets, uint32_t m, uint32_t* next, hipStream_t stream);
+// mask[order[s]] = 1 iff s < nf and state[s] is "kept", else 0, for all n sorted positions; *kept (zeroed) += the ones, one integer atomic per workgroup
+bool sample_mask(const uint32_t* order, const uint8_t* state, uint64_t n, uint32_t nf, uint8_t* mask, unsigned long long* kept, hipStream_t stream);
+
 }  // namespace pstk

@@ -11,14 +11,6 @@ using namespace pst;
 
 namespace {
 
-// the finaliser synth.hip uses for pst_buffer_synth_fill
-inline uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // The sampler's recipe (include/pasture_amd.h): ONE counter c, starting at 0, feeds every draw of a call and advances by one per draw, redraws
 // included; draw = (splitmix64(seed ^ c) * n) >> 64 from the 128-bit product.
 void sample_indices(uint64_t seed, uint64_t n, size_t iterations, uint32_t per, uint64_t* out) {

@@ -118,6 +118,15 @@ inline double checked_m2(double max_distance, const char* who) {
   return m2;
 }
 
+// the finaliser synth.hip uses for pst_buffer_synth_fill: the draws of the RANSAC sampler (ransac_api.cpp) and the shuffled priority keys of
+// the subsampling (sample_api.cpp; sample.hip evaluates the same per candidate)
+inline uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 // The raster over an AABB in x and y (pmf_api.cpp, raster_api.cpp): dim = cell of the largest coordinate + 1, by the expression the kernels
 // evaluate per point
 inline pstk::PmfGrid pmf_grid_over(double min_x, double min_y, double max_x, double max_y, double cell, const std::string& who) {
@@ -132,6 +141,30 @@ inline pstk::PmfGrid pmf_grid_over(double min_x, double min_y, double max_x, dou
   if (!fits) throw Error(PST_ERR_UNSUPPORTED, who + ": the raster would have more than 2^28 cells: use a larger cell_size");
   g.cols = (uint32_t)qx + 1;
   g.rows = (uint32_t)qy + 1;
+  return g;
+}
+
+// The uniform grid over an AABB of finite points (clusters_api.cpp, sample_api.cpp).  The edge is the tolerance times (1 + 2^-20) -- STRICTLY
+// larger, by far more than any rounding of the cell numbers (the argument is at the head of clusters.hip) -- and is doubled until no axis
+// needs more than 2^21 - 1 cells: coarser cells cost pair tests, never exactness.  dim = cell of the largest coordinate + 1, by the expression
+// the key kernel evaluates per point.
+inline pstk::ClusterGrid cluster_grid_over(const double min[3], const double max[3], double tolerance, const std::string& who) {
+  constexpr uint32_t kMaxCellsPerAxis = (1u << 21) - 1;  // 21 key bits per axis: 63 in all, and one more bit tells the all-ones key apart
+  pstk::ClusterGrid g{};
+  double extent[3];
+  for (int a = 0; a < 3; ++a) {
+    g.min[a] = min[a];
+    extent[a] = max[a] - g.min[a];
+    if (!std::isfinite(extent[a])) throw Error(PST_ERR_UNSUPPORTED, who + ": the extent of the finite points overflows f64");
+  }
+  g.edge = tolerance * (1.0 + 0x1p-20);
+  while (extent[0] / g.edge >= (double)kMaxCellsPerAxis || extent[1] / g.edge >= (double)kMaxCellsPerAxis || extent[2] / g.edge >= (double)kMaxCellsPerAxis) g.edge *= 2.0;
+  for (int a = 0; a < 3; ++a) {
+    g.dim[a] = (uint32_t)(extent[a] / g.edge) + 1;
+    uint32_t bits = 0;  // key bits that hold the cell numbers 0 .. dim - 1
+    while ((1ull << bits) < g.dim[a]) ++bits;
+    g.bits[a] = bits;
+  }
   return g;
 }
 

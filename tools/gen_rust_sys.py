@@ -117,6 +117,8 @@ pub const PST_STORAGE_INTERLEAVED: u32 = 0;
 pub const PST_STORAGE_COLUMNAR: u32 = 1;
 pub const PST_MEM_DEVICE: u32 = 0;
 pub const PST_MEM_PINNED_HOST: u32 = 1;
+pub const PST_SAMPLE_SHUFFLED: u32 = 0;
+pub const PST_SAMPLE_INDEX_ORDER: u32 = 1;
 
 #[link(name = "pasture_amd")]
 extern "C" {
