@@ -544,6 +544,63 @@ int pst_sample_kernel_shape(uint32_t* points_per_block, uint32_t* sweeps_per_lau
  * switch.  Host only. */
 int pst_sample_phase_times(double ms[3]);
 
+/* ---- Gather by index and sort orders (attribute, Morton, shuffle) ----------------------------------------------------------------------
+ * What PDAL's filters.sort, filters.mortonorder, filters.randomize and filters.head / filters.tail do, and what the index lists of
+ * pst_plane_inliers / pst_line_inliers (u64) and of the neighbour searches (u32) are for (the reference has none of it): points picked or
+ * reordered on the device.  The definitions:
+ *   gather:        dst[dst_first + j] = src[indices[j]] for j < count, every attribute, byte for byte.  The layouts are equal; either buffer
+ *                  is interleaved or columnar, owned, sliced or external, at any byte offset.  Indices may repeat, count may be larger or
+ *                  smaller than the length of src.  Interleaved to interleaved moves whole records, padding included; in the other three
+ *                  pairings record padding of an interleaved dst keeps what it held.  Nothing outside the count target points is written.
+ *   attribute key: of one scalar attribute, or of component 0 .. 2 of a Vec3 attribute.  Unsigned types: the value.  Signed types: the value
+ *                  with the sign bit flipped.  f32 / f64: -0.0 is first taken as +0.0, then key = sign ? ~bits : bits | signbit; every NaN,
+ *                  of either sign, has the all-ones key.  Ascending key order with ties in input order is numpy's
+ *                  argsort(values, kind="stable").  Descending: key' = ~key for every key that is not a NaN key: NaNs stay last and ties
+ *                  keep input order in both directions.
+ *   Morton key:    dims = 2 (x, y: PDAL's filters.mortonorder) or 3; `bits` per axis, 1 .. 31 for 2-D, 1 .. 21 for 3-D, 0 = that maximum.
+ *                  The AABB is taken over the points whose three coordinates are finite.  Per axis, on the host: inv = 2^bits / (max - min),
+ *                  0 if max == min or the quotient is not finite.  Per point and axis: t = (p - min) * inv, two separately rounded f64
+ *                  operations; c = t >= 2^bits ? 2^bits - 1 : t >= 0 ? floor(t) : 0.  Bit i of cx goes to key bit dims * i, of cy to
+ *                  dims * i + 1, of cz to dims * i + 2.  A point with a coordinate that is not finite has the key 1 << 63: it sorts last.
+ *   shuffle key:   splitmix64(seed ^ i), the key of PST_SAMPLE_SHUFFLED and of pst_sample_priorities.
+ *   order:         the stable sort of the element numbers by key: order[j] = the index of the point that comes j-th.  A buffer in that order
+ *                  is the gather by `order`.  Two calls write the same bytes.
+ * Checks, in this order.  Null arguments, index_bits not 32 / 64, an invalid memory or storage kind, dims not 2 / 3, bits out of range, a
+ * component beyond the datatype, a datatype that is not numeric (ByteArray, Custom, Vec4u8) -> PST_ERR_INVALID_ARGUMENT, answered before a
+ * device is looked for; layouts that differ -> PST_ERR_LAYOUT_MISMATCH; the attribute absent (by name and datatype), or Position3D not stored
+ * as Vec3f64 for the Morton order -> PST_ERR_MISSING_ATTRIBUTE; any byte range of src overlapping one of dst -> PST_ERR_INVALID_ARGUMENT
+ * (there is no in-place permutation); dst_first + count > the length of dst -> PST_ERR_RANGE; count == 0 and empty buffers are then PST_OK
+ * on the host; then the device: without one PST_ERR_NO_DEVICE, never a CPU path; then sort orders of 2^32 - 16 points and more ->
+ * PST_ERR_UNSUPPORTED (a gather with 64-bit indices takes any length); last, the synchronous gathers only: an index >= the length of src ->
+ * PST_ERR_RANGE with dst unchanged. */
+/* Synchronous and validated.  indices: count u32 (index_bits 32) or u64 (64) values in device memory (indices_memkind = PST_MEM_DEVICE) or
+ * host memory (anything else). */
+int pst_buffer_gather(const pst_buffer* src, const void* indices, uint32_t index_bits, uint32_t indices_memkind, size_t count, pst_buffer* dst,
+                      size_t dst_first);
+/* Stream-ordered on the current stream: no host synchronisation, no allocation.  An index >= the length of src skips its target point;
+ * device_skipped (device memory, nullable) receives the number of such entries. */
+int pst_buffer_gather_async(const pst_buffer* src, const void* device_indices, uint32_t index_bits, size_t count, pst_buffer* dst, size_t dst_first,
+                            uint64_t* device_skipped);
+/* pst_buffer_gather into a new buffer of count points and out_storage (PST_STORAGE_*); *out is the caller's to destroy. */
+int pst_buffer_take(const pst_buffer* src, const void* indices, uint32_t index_bits, uint32_t indices_memkind, size_t count, uint32_t out_storage,
+                    pst_buffer** out);
+/* The orders: d_order = len (n) u32 values in device memory.  Synchronous; the sorts' scratch is allocated on the stream and released. */
+int pst_sort_order_by_attribute_device(const pst_buffer* b, const char* name, const pst_datatype* dt, uint32_t component, uint32_t descending,
+                                       uint32_t* d_order);
+/* d_keys (device, nullable): also the key of point i, len u64 values */
+int pst_morton_order_device(const pst_buffer* b, uint32_t dims, uint32_t bits, uint32_t* d_order, uint64_t* d_keys);
+int pst_shuffle_order_device(uint64_t n, uint64_t seed, uint32_t* d_order);
+/* d_inverse[d_order[j]] = j for j < n; entries >= n are skipped.  Stream-ordered.  The two arrays are different ones. */
+int pst_invert_order_device(const uint32_t* d_order, uint64_t n, uint32_t* d_inverse);
+/* The gather kernel's seams (tests place their sizes around them; each pointer optional): consecutive output points one workgroup owns, and
+ * the bytes of the LDS record tile of the pairings with an interleaved side (records of which fewer than 16 fit it take a plain byte-copy
+ * kernel).  Host only. */
+int pst_reorder_kernel_shape(uint32_t* points_per_block, uint32_t* record_tile_bytes);
+/* Measurement aid.  With PST_REORDER_TIMES=1 in the environment the synchronous calls above bracket their phases with stream events; this
+ * returns the calling thread's last such call: ms = {bounds and keys, sort, gather}, a phase the call does not have as 0.  Zeros without the
+ * switch.  Host only. */
+int pst_reorder_phase_times(double ms[3]);
+
 /* ---- Ground classification (progressive morphological filter) ------------------------------------------------------------------------
  * What PDAL's filters.pmf and PCL's ProgressiveMorphologicalFilter compute (Zhang et al. 2003; the reference has neither), with square
  * windows: the points are rasterised to their lowest z per cell, the raster is opened (eroded, then dilated) with growing windows, and a

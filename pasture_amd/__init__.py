@@ -19,6 +19,8 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          pmf_schedule, remove_ground, classification_mask, hag_kernel_shape, hag_phase_times, height_above_ground,
                          height_above_ground_device, normalize_height, Raster, grid_fill, raster_kernel_shape, raster_phase_times, rasterize,
                          FEATURES, features_kernel_shape, geometric_features, geometric_features_device,
-                         poisson_disk_mask, sample_kernel_shape, sample_phase_times, sample_priorities, subsample_min_distance)
+                         poisson_disk_mask, sample_kernel_shape, sample_phase_times, sample_priorities, subsample_min_distance,
+                         argsort_attribute, invert_order, morton_order, morton_sort, reorder_kernel_shape, reorder_phase_times, shuffle, shuffle_order,
+                         sort_by_attribute)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

@@ -235,6 +235,15 @@ _PRODUCT_SIGNATURES = {
     "sample_priorities": [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _U64P],
     "sample_kernel_shape": [_U32P, _U32P],
     "sample_phase_times": [_D3],
+    "buffer_gather": [_P, _P, C.c_uint32, C.c_uint32, _SZ, _P, _SZ],
+    "buffer_gather_async": [_P, _P, C.c_uint32, _SZ, _P, _SZ, _P],
+    "buffer_take": [_P, _P, C.c_uint32, C.c_uint32, _SZ, C.c_uint32, _PP],
+    "sort_order_by_attribute_device": [_P, C.c_char_p, _DT, C.c_uint32, C.c_uint32, _P],
+    "morton_order_device": [_P, C.c_uint32, C.c_uint32, _P, _P],
+    "shuffle_order_device": [C.c_uint64, C.c_uint64, _P],
+    "invert_order_device": [_P, C.c_uint64, _P],
+    "reorder_kernel_shape": [_U32P, _U32P],
+    "reorder_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

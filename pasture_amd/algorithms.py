@@ -1147,3 +1147,107 @@ def sample_phase_times(api=None):
     ms = (C.c_double * 3)()
     (api or product_api()).sample_phase_times(ms)
     return tuple(ms)
+
+
+# ---- gather by index and sort orders: attribute, Morton, shuffle (include/pasture_amd.h) ----------------------------------------------------
+
+def _order_result(api, n: int, device_order_ptr, call):
+    """call(address of n u32) fills the order: into the caller's device memory (returns None), or into a numpy uint32 array"""
+    from .layout import PointAttributeDataType as T
+    if device_order_ptr is not None:
+        call(C.c_void_p(int(device_order_ptr) or None))
+        return None
+    out = _DeviceArray(api, T.U32, n)
+    call(C.c_void_p(out.ptr or (None if n else 1)))
+    return out.to_numpy()
+
+
+def argsort_attribute(buffer: _Buffer, attribute: PointAttributeDefinition, component: int = 0, descending: bool = False, device_order_ptr: Optional[int] = None):
+    """np.argsort(values, kind="stable") of one numeric attribute (component 0 .. 2 of a Vec3 one) on the device: NaNs last, ties in input
+    order in both directions.  Returns a numpy uint32 array, or None when the order went to DEVICE memory at device_order_ptr."""
+    cdt = attribute.datatype().to_c()
+    return _order_result(buffer.api, buffer.len(), device_order_ptr,
+                         lambda p: buffer.api.sort_order_by_attribute_device(buffer._h, attribute.name().encode(), C.byref(cdt), component, 1 if descending else 0, p))
+
+
+def morton_order(buffer: _Buffer, dims: int = 3, bits: int = 0, device_order_ptr: Optional[int] = None, return_keys: bool = False):
+    """The Z-order of the cloud (PDAL's filters.mortonorder with dims=2): `bits` per axis over the AABB of the finite points (0: 21 for three
+    axes, 31 for two); points with a coordinate that is not finite come last.  Returns the order as argsort_attribute does; with return_keys
+    (order, keys): the uint64 key of every point."""
+    from .layout import PointAttributeDataType as T
+    keys = _DeviceArray(buffer.api, T.U64, buffer.len()) if return_keys else None
+    order = _order_result(buffer.api, buffer.len(), device_order_ptr,
+                          lambda p: buffer.api.morton_order_device(buffer._h, dims, bits, p, C.c_void_p(keys.ptr or None) if keys else None))
+    return (order, keys.to_numpy()) if return_keys else order
+
+
+def shuffle_order(n: int, seed: int, device_order_ptr: Optional[int] = None, api=None):
+    """The permutation that sorts 0 .. n - 1 by splitmix64(seed ^ i): the argsort of sample_priorities("shuffled", seed, 0, n)."""
+    from ._capi import product_api
+    api = api or product_api()
+    return _order_result(api, n, device_order_ptr, lambda p: api.shuffle_order_device(n, seed & 0xFFFFFFFFFFFFFFFF, p))
+
+
+def invert_order(order, device_inverse_ptr: Optional[int] = None, api=None):
+    """inverse[order[j]] = j: a per-point result computed on a reordered cloud is carried back with result[inverse].  `order`: a numpy
+    array, or a (device_ptr, n) pair."""
+    from ._capi import product_api
+    from .layout import PointAttributeDataType as T
+    api = api or product_api()
+    staged = None
+    if isinstance(order, tuple):
+        ptr, n = int(order[0]), int(order[1])
+    else:
+        order = np.ascontiguousarray(order, dtype=np.uint32)
+        n = order.size
+        staged = _DeviceArray(api, T.U32, n)
+        if n:
+            staged.buffer.set_attribute_range(staged.attribute, range(0, n), order)
+        ptr = staged.ptr
+    result = _order_result(api, n, device_inverse_ptr, lambda p: api.invert_order_device(C.c_void_p(ptr or None), n, p))
+    if staged is not None and device_inverse_ptr is not None:
+        api.stream_synchronize()  # the staged copy of the order is released on return
+    return result
+
+
+def _take_by_device_order(buffer: _Buffer, out_buffer_type, fill, return_order: bool = False):
+    """fill(address of len(buffer) u32) writes an order; the points in that order, the list never leaving the device"""
+    from .layout import PointAttributeDataType as T
+    n = buffer.len()
+    order = _DeviceArray(buffer.api, T.U32, n)
+    result = fill(order.ptr or 1)
+    out = buffer.take((order.ptr, n, 32), out_buffer_type)
+    return (out, order.to_numpy(), result) if return_order else (out, None, result)
+
+
+def sort_by_attribute(buffer: _Buffer, attribute: PointAttributeDefinition, component: int = 0, descending: bool = False, out_buffer_type=None):
+    """PDAL's filters.sort: a new buffer with the points in argsort_attribute's order."""
+    return _take_by_device_order(buffer, out_buffer_type, lambda p: argsort_attribute(buffer, attribute, component, descending, device_order_ptr=p))[0]
+
+
+def morton_sort(buffer: _Buffer, dims: int = 3, bits: int = 0, out_buffer_type=None, return_order: bool = False):
+    """A new buffer with the points in morton_order's order; with return_order (buffer, order)."""
+    out, order, _ = _take_by_device_order(buffer, out_buffer_type, lambda p: morton_order(buffer, dims, bits, device_order_ptr=p), return_order)
+    return (out, order) if return_order else out
+
+
+def shuffle(buffer: _Buffer, seed: int, out_buffer_type=None):
+    """PDAL's filters.randomize with a seed: a new buffer with the points in shuffle_order(len(buffer), seed)."""
+    return _take_by_device_order(buffer, out_buffer_type, lambda p: shuffle_order(buffer.len(), seed, device_order_ptr=p, api=buffer.api))[0]
+
+
+def reorder_kernel_shape(api=None) -> dict:
+    """The seams of the gather kernel: consecutive output points one workgroup owns, bytes of its LDS record tile."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).reorder_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "record_tile_bytes"), (x.value for x in v)))
+
+
+def reorder_phase_times(api=None):
+    """(bounds and keys, sort, gather) in milliseconds of this thread's last synchronous gather or sort-order call; zeros unless
+    PST_REORDER_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 3)()
+    (api or product_api()).reorder_phase_times(ms)
+    return tuple(ms)

@@ -209,6 +209,46 @@ class _Buffer:
         of mask hits lands in the 8 bytes at device_count_ptr (optional) in stream order."""
         self.api.buffer_filter_into_async(self._h, buffer._h, C.c_void_p(int(device_mask_ptr)), num_matches, C.c_void_p(int(device_count_ptr) or None))
 
+    # gather by index (include/pasture_amd.h, "Gather by index and sort orders") -----------------------------------
+    @staticmethod
+    def _index_arg(indices):
+        """A numpy u32 / u64 / i64 array (i64 is what numpy hands out: checked non-negative and taken as u64), or a (device_ptr, count,
+        bits) triple for a list that already lives in device memory.  Returns (pointer, bits, memkind, count, keepalive)."""
+        if isinstance(indices, tuple) and len(indices) == 3:
+            ptr, count, bits = indices
+            return C.c_void_p(int(ptr) or None), int(bits), MEM_DEVICE, int(count), None
+        arr = np.ascontiguousarray(np.asarray(indices))
+        if arr.ndim != 1:
+            raise ValueError("indices must be one-dimensional")
+        if arr.dtype == np.int64:
+            if arr.size and int(arr.min()) < 0:
+                raise ValueError("indices must not be negative")
+            arr = arr.view(np.uint64)
+        if arr.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
+            raise TypeError("indices must be a numpy array of uint32, uint64 or int64")
+        return C.c_void_p(arr.ctypes.data if arr.size else None), 8 * arr.dtype.itemsize, MEM_PINNED_HOST, arr.size, arr
+
+    def take(self, indices, out_buffer_type=None):
+        """A new buffer of the points `indices` names, in that order: out[j] = self[indices[j]]."""
+        ptr, bits, kind, count, keep = self._index_arg(indices)
+        out_buffer_type = out_buffer_type or (HashMapBuffer if self.as_columnar() is not None else VectorBuffer)
+        h = C.c_void_p()
+        self.api.buffer_take(self._h, ptr, bits, kind, count, out_buffer_type._storage, C.byref(h))
+        return out_buffer_type(h.value, self.api)
+
+    def gather_into(self, dst: "_Buffer", indices, dst_first: int = 0) -> None:
+        """dst[dst_first + j] = self[indices[j]]; synchronous, an index beyond this buffer is status 3 with dst unchanged."""
+        ptr, bits, kind, count, keep = self._index_arg(indices)
+        self.api.buffer_gather(self._h, ptr, bits, kind, count, dst._h, dst_first)
+
+    def gather_into_async(self, dst: "_Buffer", device_indices, dst_first: int = 0, device_skipped_ptr: int = 0) -> None:
+        """Stream-ordered gather_into for a (device_ptr, count, bits) list: nothing waits on the host; an index beyond this buffer skips
+        its target point, and the number of such entries lands in the 8 bytes at device_skipped_ptr (optional) in stream order."""
+        ptr, bits, kind, count, keep = self._index_arg(device_indices)
+        if kind != MEM_DEVICE:
+            raise TypeError("gather_into_async takes a (device_ptr, count, bits) triple")
+        self.api.buffer_gather_async(self._h, ptr, bits, count, dst._h, dst_first, C.c_void_p(int(device_skipped_ptr) or None))
+
     # device-side helpers ---------------------------------------------------------------------------------
     def synth_fill(self, seed: int, first_index: int = 0) -> None:
         self.api.buffer_synth_fill(self._h, seed, first_index)

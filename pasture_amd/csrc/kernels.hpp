@@ -398,4 +398,47 @@ bool sample_compact(const uint32_t* active, const uint32_t* flags, const unsigne
 // mask[order[s]] = 1 iff s < nf and state[s] is "kept", else 0, for all n sorted positions; *kept (zeroed) += the ones, one integer atomic per workgroup
 bool sample_mask(const uint32_t* order, const uint8_t* state, uint64_t n, uint32_t nf, uint8_t* mask, unsigned long long* kept, hipStream_t stream);
 
+// Gather by index and the keys of the device sort orders (reorder.hip; the checks, the scratch and the order of the launches are in
+// reorder_api.cpp).  The seams (pst_reorder_kernel_shape):
+constexpr uint32_t kReorderPointsPerBlock = 256;      // consecutive OUTPUT points one workgroup owns: one index per lane, read once
+constexpr uint32_t kReorderRecordTileBytes = 32768;   // LDS record tile of the paths with an interleaved side, slack included
+constexpr uint32_t kReorderTileSlack = 48;            // 16 bytes of target misalignment in front, 32 behind (lds_load reads past a value)
+constexpr uint32_t kReorderMinTileRecords = 16;       // records with fewer than this many per tile take the byte-copy kernel
+constexpr int kReorderMaxAttrs = 48;                  // attributes per launch; layouts with more are gathered in several launches
+// one attribute of a gather: src = address of the attribute of source point 0, dst = of target point dst_first; offset = in the record
+struct GatherAttr { uint64_t src, dst; uint32_t src_stride, dst_stride, offset, size; };
+struct GatherArgs {
+  const void* idx;              // count indices, u32 or u64 (idx64), device memory
+  uint64_t count, src_len;
+  uint64_t src_rec, dst_rec;    // interleaved sides: address of source record 0 / of target record dst_first
+  uint32_t idx64, stride;       // stride: the record size (both layouts are equal)
+  uint32_t chunk;               // records per pass over the LDS record tile
+  uint32_t n_attrs;
+  uint32_t dst_covered;         // the attributes cover every byte of a record: a tile without skipped points need not be read first
+  uint32_t count_skipped;       // add the out-of-range entries to *skipped (one launch of a call does)
+  unsigned long long* skipped;  // nullable
+  GatherAttr attrs[kReorderMaxAttrs];
+};
+uint32_t gather_chunk(uint32_t stride);      // records per LDS tile pass; below kReorderMinTileRecords: gather_tile_fits is false
+bool gather_tile_fits(uint32_t stride);
+// dst[dst_first + j] = src[idx[j]], j < count; an index >= src_len leaves its target point alone and is counted.  by_bytes: the plain
+// per-attribute byte-copy kernel (any record size).  Interleaved to interleaved in the tile kernel moves whole records (a.attrs unused).
+bool gather_points(const GatherArgs& a, bool src_aos, bool dst_aos, bool by_bytes, hipStream_t stream);
+// out2[0] = max index, out2[1] = entries >= src_len (both zeroed by the caller)
+bool gather_index_check(const void* idx, bool idx64, uint64_t count, uint64_t src_len, unsigned long long* out2, hipStream_t stream);
+// Sort keys of one component of a numeric attribute (the value of point i at addr + i * stride; ct: its component type): ascending key order
+// is np.argsort(values, kind="stable") with NaNs last; descending complements every key that is not a NaN key.  keys32 for types of up to
+// 32 bits, else keys64 and vals[i] = i.
+bool reorder_attribute_keys(uint64_t addr, uint64_t stride, uint64_t n, uint32_t ct, bool descending, uint32_t* keys32, unsigned long long* keys64, uint32_t* vals,
+                            hipStream_t stream);
+// cell = clamp(floor((p - min) * inv)) per axis, `bits` bits each, interleaved x lowest; dims 2 (x, y) or 3
+struct MortonGrid { double min[3], inv[3]; uint32_t dims, bits; };
+// sort_keys[i]: the Morton key, bit dims * bits set alone for a point with a coordinate that is not finite; vals[i] = i; out_keys (nullable):
+// the same with 1 << 63 for those points
+bool reorder_morton_keys(const Positions& pos, const MortonGrid& g, unsigned long long* sort_keys, uint32_t* vals, unsigned long long* out_keys, hipStream_t stream);
+// keys[i] = splitmix64(seed ^ i), vals[i] = i
+bool reorder_shuffle_keys(uint64_t n, uint64_t seed, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
+// inverse[order[j]] = j for every order[j] < n
+bool reorder_invert(const uint32_t* order, uint64_t n, uint32_t* inverse, hipStream_t stream);
+
 }  // namespace pstk
