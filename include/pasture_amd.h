@@ -500,6 +500,55 @@ int pst_cluster_kernel_shape(uint32_t* points_per_block, uint32_t* tile_points);
  * switch.  Host only. */
 int pst_cluster_phase_times(double ms[3]);
 
+/* ---- DBSCAN (core, border and noise points) ---------------------------------------------------------------------------------------------
+ * What PDAL's filters.dbscan and scikit-learn's DBSCAN compute (the reference has neither): clusters are carried by the points that have
+ * enough neighbours; points on the rim are attached to a cluster but never bridge two; the rest is noise.  Where pst_euclidean_clusters joins
+ * everything that touches -- two objects linked by a thread of stray returns become one, every isolated return is a cluster of its own --
+ * this call keeps the objects apart and the strays out.  The definition:
+ *   finite point:  as for the clusters.  A point with a NaN or +-inf coordinate is neither core nor border, is nobody's neighbour, and gets
+ *                  the label 0xFFFFFFFF.
+ *   neighbour:     finite points i and j are neighbours iff (dx*dx + dy*dy) + dz*dz <= e2, dx = pj.x - pi.x (y, z alike), every operation a
+ *                  separately rounded f64 operation, e2 = eps * eps rounded once on the host.  There is no sqrt.  This is the adjacency of
+ *                  pst_euclidean_clusters and the conflict of pst_poisson_disk_mask, on purpose.  A finite point is its own neighbour.
+ *   core:          finite point i is a core point iff the number of its neighbours, ITSELF INCLUDED, is >= min_points (scikit-learn's
+ *                  min_samples, PDAL's min_points).
+ *   cluster:       a connected component of the neighbour graph restricted to the CORE points.
+ *   border:        a finite point that is not core and has at least one core neighbour.  It joins the cluster of the core neighbour with
+ *                  the smallest d2 (the sum above), ties to the core neighbour with the smallest index in the buffer.  Nothing is united
+ *                  through it.  Sequential DBSCAN gives a border point to whichever cluster reaches it first, which depends on the order
+ *                  of the visit; this rule is the order-free choice.  Core points, noise points and the partition of the core points are
+ *                  exactly scikit-learn's and PDAL's; only a border point within eps of two clusters may go to the other one there.
+ *   noise:         every other point; label 0xFFFFFFFF.
+ *   numbering:     the clusters are numbered 0, 1, ... by descending size (core + border members), ties by ascending smallest member index
+ *                  (index in the buffer): the clusters' rule.  There is no size filter: min_points is the filter.
+ * The result depends on nothing else: not on the grid, the schedule, the storage or the launch shape.  Two calls on one cloud write the same
+ * bytes (sizes are integer sums, the border choice is a minimum, the numbering is a stable sort).  Two consequences:
+ *   min_points == 1: labels and sizes are byte for byte those of pst_euclidean_clusters(eps, 1, UINT64_MAX) -- every finite point is core.
+ *   min_points == 2: they are those of pst_euclidean_clusters(eps, 2, UINT64_MAX) -- every member of a component of two or more points has
+ *                    at least two neighbours, so there are no border points, and the singletons are noise.
+ * Null b, labels or counts, an invalid memkind, eps not finite, not > 0 or with eps * eps not a normal number, min_points == 0 ->
+ * PST_ERR_INVALID_ARGUMENT, answered before a device is looked for; Position3D not stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE
+ * (interleaved or columnar, owned, sliced or external, at any byte offset); without a device PST_ERR_NO_DEVICE, never a CPU path; 2^32 - 16
+ * points and more -> PST_ERR_UNSUPPORTED (so is a cloud whose finite extent overflows f64).  Any length from 0 up is legal: an empty cloud
+ * has zero counts (answered on the host); a cloud without a finite point gets all-0xFFFFFFFF labels, zero core bytes and zero counts;
+ * min_points above the number of finite points is legal and makes everything noise.
+ * Cost: the index build of pst_euclidean_clusters, one walk of the 27 neighbouring grid cells per point that stops at min_points neighbours,
+ * the clusters' traversal over the core points, and one more walk of the 27 cells for every point that is not core. */
+/* Synchronous.  labels: len x uint32, required; core: len bytes, nullable, 1 = core point, 0 otherwise (scikit-learn's
+ * core_sample_indices_ as a mask that pst_buffer_filter takes).  Both in device memory (memkind = PST_MEM_DEVICE) or both in host memory
+ * (anything else), the convention of the cluster labels.  sizes (host, nullable): sizes[c] = points of cluster c, when the clusters fit
+ * sizes_capacity; more clusters than that -> PST_ERR_RANGE with the counts set and the labels written.
+ * counts = {clusters, core points, labelled points (core + border)}.  pst_cluster_mask_device turns the labels into a filter mask. */
+int pst_dbscan(const pst_buffer* b, double eps, uint64_t min_points, uint32_t* labels, uint8_t* core, uint32_t memkind, uint64_t* sizes,
+               size_t sizes_capacity, uint64_t counts[3]);
+/* The seam of the count, link and border kernels (tests place their sizes around it; the pointer is optional): points one workgroup owns,
+ * one lane each.  Host only. */
+int pst_dbscan_kernel_shape(uint32_t* points_per_block);
+/* Measurement aid.  With PST_DBSCAN_TIMES=1 in the environment pst_dbscan brackets its four phases with stream events; this returns the
+ * calling thread's last call: ms = {index build (AABB, keys, sort, gather), core count, link, border + bookkeeping}.  Zeros without the
+ * switch.  Host only. */
+int pst_dbscan_phase_times(double ms[4]);
+
 /* ---- Minimum-distance (Poisson-disk) subsampling ----------------------------------------------------------------------------------------
  * What PDAL's filters.sample, CloudCompare's "subsample by space" and lidR's decimate_points compute (the reference has none of them): a
  * subset of the ORIGINAL points in which no two are closer than a radius, as a byte mask that pst_buffer_filter / pst_buffer_filter_into

@@ -235,6 +235,9 @@ _PRODUCT_SIGNATURES = {
     "sample_priorities": [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, _U64P],
     "sample_kernel_shape": [_U32P, _U32P],
     "sample_phase_times": [_D3],
+    "dbscan": [_P, C.c_double, C.c_uint64, _P, _P, C.c_uint32, _U64P, _SZ, _U64P],
+    "dbscan_kernel_shape": [_U32P],
+    "dbscan_phase_times": [_D3],
     "buffer_gather": [_P, _P, C.c_uint32, C.c_uint32, _SZ, _P, _SZ],
     "buffer_gather_async": [_P, _P, C.c_uint32, _SZ, _P, _SZ, _P],
     "buffer_take": [_P, _P, C.c_uint32, C.c_uint32, _SZ, C.c_uint32, _PP],

@@ -491,6 +491,75 @@ def cluster_phase_times(api=None):
     return tuple(ms)
 
 
+# ---- DBSCAN (include/pasture_amd.h) ------------------------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class DbscanResult:
+    labels: Optional[np.ndarray]  # uint32, NO_CLUSTER for noise and non-finite points; None when they went to device memory
+    core: Optional[np.ndarray]    # bool, True for core points; None when it went to device memory
+    sizes: np.ndarray             # uint64, sizes[c] = core + border points of cluster c
+    n_core: int
+    n_labelled: int
+
+
+def dbscan(buffer: _Buffer, eps: float, min_points: int, device_labels_ptr: Optional[int] = None, device_core_ptr: Optional[int] = None) -> DbscanResult:
+    """PDAL's filters.dbscan / scikit-learn's DBSCAN on the device: a finite point with at least `min_points` points within `eps` (itself
+    included) is a core point; clusters are the connected components of the core points; a point that is not core joins the cluster of its
+    nearest core neighbour (ties: smallest buffer index) and bridges nothing; the rest is noise.  Clusters are numbered by descending size
+    (ties: ascending smallest member index).  With device_labels_ptr the len(buffer) uint32 labels and, at device_core_ptr (optional), the
+    len(buffer) core bytes go to DEVICE memory and the result's labels / core are None.
+    Two calls: the first writes labels and core flags and reports the number of clusters, the second fetches that many sizes."""
+    n = buffer.len()
+    on_device = device_labels_ptr is not None
+    if device_core_ptr is not None and not on_device:
+        raise ValueError("device_core_ptr needs device_labels_ptr: labels and core flags share one memory kind")
+    labels = None if on_device else np.full(n, NO_CLUSTER, dtype=np.uint32)
+    core = None if on_device else np.zeros(n, dtype=np.uint8)
+    if on_device:
+        lptr, cptr = C.c_void_p(int(device_labels_ptr) or None), C.c_void_p(int(device_core_ptr) if device_core_ptr else None)
+    else:
+        lptr, cptr = C.c_void_p(labels.ctypes.data if n else 1), C.c_void_p(core.ctypes.data if n else 1)
+    kind = 0 if on_device else 1
+    counts = (C.c_uint64 * 3)()
+    call = buffer.api.dbscan
+    call(buffer._h, eps, min_points, lptr, cptr, kind, None, 0, counts)
+    sizes = np.zeros(counts[0], dtype=np.uint64)
+    if counts[0]:
+        call(buffer._h, eps, min_points, lptr, cptr, kind, _u64(sizes), counts[0], counts)
+    return DbscanResult(labels, None if core is None else core.astype(bool), sizes, int(counts[1]), int(counts[2]))
+
+
+def extract_dbscan_clusters(buffer: _Buffer, eps: float, min_points: int, first_cluster: int = 0, cluster_count: int = 1, out_buffer_type=None):
+    """(the points of DBSCAN clusters first_cluster .. first_cluster + cluster_count - 1 in buffer order with all their attributes, sizes of
+    ALL clusters): labels and mask stay in device memory.  cluster_count = 0xFFFFFFFF from cluster 0 drops the noise and keeps the rest.
+    `buffer` is columnar (filter is defined on HashMapBuffer)."""
+    from .layout import PointAttributeDataType as T
+    labels = _DeviceArray(buffer.api, T.U32, buffer.len())
+
+    def fill(mask_ptr):
+        sizes = dbscan(buffer, eps, min_points, device_labels_ptr=labels.ptr or 1).sizes
+        cluster_mask(labels.ptr, buffer.len(), first_cluster, cluster_count, mask_ptr, api=buffer.api)
+        return sizes
+    return _filter_by_device_mask(buffer, out_buffer_type, fill)
+
+
+def dbscan_kernel_shape(api=None) -> dict:
+    """The seam of the count, link and border kernels: points one workgroup owns, one lane each."""
+    from ._capi import product_api
+    v = C.c_uint32()
+    (api or product_api()).dbscan_kernel_shape(C.byref(v))
+    return {"points_per_block": v.value}
+
+
+def dbscan_phase_times(api=None):
+    """(index build, core count, link, border + bookkeeping) in milliseconds of this thread's last dbscan call; zeros unless
+    PST_DBSCAN_TIMES=1 was set when the library first ran one."""
+    from ._capi import product_api
+    ms = (C.c_double * 4)()
+    (api or product_api()).dbscan_phase_times(ms)
+    return tuple(ms)
+
+
 # ---- ground classification: the progressive morphological filter (include/pasture_amd.h) -------------------------------------------------------
 
 @dataclass(frozen=True)

@@ -28,7 +28,7 @@
 // no lane ever waits for another lane's write.  The parent reads inside the kernel are agent-scope relaxed loads; a read that is stale (the
 // XCDs' L2s are not coherent) still returns a former parent, which is a member of the same set with a lower id, so it costs steps, never
 // correctness: only the CAS decides who is a root, and it executes at the memory side.
-#include "positions_device.hpp"
+#include "grid_index_device.hpp"
 
 using namespace pstd;
 
@@ -107,45 +107,7 @@ __global__ __launch_bounds__(kBlock) void cluster_gather_kernel(Pos pos, const u
   parent[s] = s;
 }
 
-// ---- union-find -------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t parent_of(const uint32_t* parent, uint32_t v) {
-  return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the root of v's set as far as this lane can see, halving the path on the way: every value stored is an ancestor, and below what it replaces
-__device__ __forceinline__ uint32_t find_root(uint32_t* parent, uint32_t v) {
-  for (;;) {
-    const uint32_t p = parent_of(parent, v);
-    if (p == v) return v;
-    const uint32_t gp = parent_of(parent, p);
-    if (gp == p) return p;
-    atomicMin(parent + v, gp);
-    v = gp;
-  }
-}
-__device__ __forceinline__ void unite(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    const uint32_t seen = atomicCAS(parent + hi, hi, lo);
-    if (seen == hi) return;
-    a = seen;  // hi is no root any more: its parent `seen` < hi is where the search goes on -- strictly lower every time round
-    b = lo;
-  }
-}
-
-// first position in keys[0, end) whose key is >= k
-__device__ __forceinline__ uint32_t lower_bound(const unsigned long long* __restrict__ keys, uint32_t end, unsigned long long k) {
-  uint32_t lo = 0, hi = end;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// ---- the traversal ----------------------------------------------------------------------------------------------------------------------------
+// ---- the traversal (the union-find and the binary search of the keys: grid_index_device.hpp) ----------------------------------------------------
 __global__ __launch_bounds__(kBlock) void cluster_traverse_kernel(const unsigned long long* __restrict__ keys, const double* __restrict__ xs, const double* __restrict__ ys,
                                                                   const double* __restrict__ zs, uint32_t nf, Grid g, double t2, uint32_t* parent) {
   const uint32_t s = blockIdx.x * kP + threadIdx.x;

@@ -398,6 +398,29 @@ bool sample_compact(const uint32_t* active, const uint32_t* flags, const unsigne
 // mask[order[s]] = 1 iff s < nf and state[s] is "kept", else 0, for all n sorted positions; *kept (zeroed) += the ones, one integer atomic per workgroup
 bool sample_mask(const uint32_t* order, const uint8_t* state, uint64_t n, uint32_t nf, uint8_t* mask, unsigned long long* kept, hipStream_t stream);
 
+// DBSCAN (dbscan.hip; the checks, the scratch and the order of the launches are in dbscan_api.cpp).  The index is the cluster index:
+// cluster_bounds, cluster_keys on a ClusterGrid, the 64-bit sort, nn_gather.  The seam (pst_dbscan_kernel_shape):
+constexpr uint32_t kDbscanPointsPerBlock = 256;  // points one workgroup of the count, link and border kernels owns, one lane each
+// core[s] = 1 iff sorted point s has at least min_points neighbours, itself included (1 <= min_points <= nf); parent[s] = s; *n_core (zeroed) +=
+// the core points, one integer atomic per wave
+bool dbscan_count(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, uint32_t nf, const ClusterGrid& g, double e2,
+                  uint32_t min_points, uint8_t* core, uint32_t* parent, unsigned long long* n_core, hipStream_t stream);
+// the cluster traversal over the core points alone: unite(s, c) for core neighbours s > c
+bool dbscan_link(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, const uint8_t* core, uint32_t nf, const ClusterGrid& g,
+                 double e2, uint32_t* parent, hipStream_t stream);
+// behind dbscan_link: root[s] = the root of a core point / of the core neighbour of smallest (d2, buffer index) / 0xFFFFFFFF for noise; points
+// per root and the smallest buffer index per root (both set up here)
+bool dbscan_border(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, const uint8_t* core, const uint32_t* order, uint32_t nf,
+                   const ClusterGrid& g, double e2, uint32_t* parent, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream);
+// flags[i] = 1 and root_at[i] = root where i is the smallest member of a cluster (flags: n + 1 elements, the last one 0); *n_labelled
+// (zeroed) += the sizes.  cluster_list_kept takes it from there.
+bool dbscan_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint64_t n, uint32_t nf, uint32_t* flags, uint32_t* root_at,
+                 unsigned long long* n_labelled, hipStream_t stream);
+// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[order[s]] = rank of root[s], 0xFFFFFFFF without one;
+// core_out[order[s]] = core[s], 0 for the non-finite points (core_out nullable)
+bool dbscan_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t clusters, const uint32_t* order, const uint32_t* root, const uint8_t* core, uint64_t n,
+                   uint32_t nf, uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, uint8_t* core_out, hipStream_t stream);
+
 // Gather by index and the keys of the device sort orders (reorder.hip; the checks, the scratch and the order of the launches are in
 // reorder_api.cpp).  The seams (pst_reorder_kernel_shape):
 constexpr uint32_t kReorderPointsPerBlock = 256;      // consecutive OUTPUT points one workgroup owns: one index per lane, read once

@@ -28,7 +28,7 @@
 // Traffic per candidate: the state byte first (a rejected candidate costs nothing more -- from the second round on most are), then the three
 // coordinates (24 bytes), then, only where it conflicts, its buffer index (4 bytes) from which the priority key is recomputed (ten integer
 // operations); storing the keys next to the positions would read 8 bytes there instead and write 8 bytes per point in the gather.
-#include "positions_device.hpp"
+#include "grid_index_device.hpp"
 
 using namespace pstd;
 
@@ -113,16 +113,6 @@ __device__ __forceinline__ unsigned long long priority_of(uint32_t shuffled, uns
 }
 
 __device__ __forceinline__ uint8_t state_of(const uint8_t* state, uint32_t s) { return __hip_atomic_load(state + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// first position in keys[0, end) whose key is >= k
-__device__ __forceinline__ uint32_t lower_bound(const unsigned long long* __restrict__ keys, uint32_t end, unsigned long long k) {
-  uint32_t lo = 0, hi = end;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // active == nullptr: the first round, every sorted point is active (m == nf).  flags: m + 1 entries, flags[t] = 1 iff active point t leaves
 // the launch undecided, flags[m] = 0 (the scan's last offset is their number).
