@@ -40,6 +40,14 @@ class AABB:
         return AABB(tuple(x if x < y else y for x, y in zip(a._min, b._min)), tuple(x if x > y else y for x, y in zip(a._max, b._max)))
 
 
+def _phase_times(api, entry: str, phases: int):
+    """the `phases` milliseconds behind pst_<entry>: what every *_phase_times below returns"""
+    from ._capi import product_api
+    ms = (C.c_double * phases)()
+    getattr(api or product_api(), entry)(ms)
+    return tuple(ms)
+
+
 def calculate_bounds(buffer: _Buffer) -> Optional[AABB]:
     mn, mx, has = (C.c_double * 3)(), (C.c_double * 3)(), C.c_int()
     buffer.api.calculate_bounds(buffer._h, mn, mx, C.byref(has))
@@ -485,10 +493,7 @@ def cluster_kernel_shape(api=None) -> dict:
 def cluster_phase_times(api=None):
     """(index build, traversal + union, bookkeeping) in milliseconds of this thread's last euclidean_clusters call; zeros unless
     PST_CLUSTER_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).cluster_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "cluster_phase_times", 3)
 
 
 # ---- DBSCAN (include/pasture_amd.h) ------------------------------------------------------------------------------------------------------------
@@ -554,10 +559,7 @@ def dbscan_kernel_shape(api=None) -> dict:
 def dbscan_phase_times(api=None):
     """(index build, core count, link, border + bookkeeping) in milliseconds of this thread's last dbscan call; zeros unless
     PST_DBSCAN_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 4)()
-    (api or product_api()).dbscan_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "dbscan_phase_times", 4)
 
 
 # ---- ground classification: the progressive morphological filter (include/pasture_amd.h) -------------------------------------------------------
@@ -691,10 +693,7 @@ def pmf_kernel_shape(api=None) -> dict:
 def pmf_phase_times(api=None):
     """(bounds + raster, morphology, classification) in milliseconds of this thread's last ground_mask call; zeros unless PST_PMF_TIMES=1 was
     set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).pmf_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "pmf_phase_times", 3)
 
 
 # ---- nearest neighbours between two clouds, ICP (include/pasture_amd.h) ----------------------------------------------------------------------
@@ -876,10 +875,7 @@ def nn_kernel_shape(api=None) -> dict:
 def nn_phase_times(api=None):
     """(query keys + sort, search) in milliseconds of this thread's last nearest_neighbours* call; zeros unless PST_NN_TIMES=1 was set when the
     library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 2)()
-    (api or product_api()).nn_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "nn_phase_times", 2)
 
 
 # ---- height above ground from the k nearest ground points in the XY plane (include/pasture_amd.h) ---------------------------------------------
@@ -970,10 +966,7 @@ def hag_kernel_shape(api=None) -> dict:
 def hag_phase_times(api=None):
     """(ground bounds + keys + sort + directory, query keys + sort, search) in milliseconds of this thread's last height_above_ground* call;
     zeros unless PST_HAG_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).hag_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "hag_phase_times", 3)
 
 
 # ---- rasterisation: per-cell statistics on an XY grid, and the hole filler (include/pasture_amd.h) --------------------------------------------
@@ -1077,10 +1070,7 @@ def raster_kernel_shape(api=None) -> dict:
 def raster_phase_times(api=None):
     """(bounds, keys + sort + directory, reduction + output) in milliseconds of this thread's last rasterize call; zeros unless
     PST_RASTER_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).raster_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "raster_phase_times", 3)
 
 
 # ---- geometric features from the eigenvalues of the neighbourhood covariance (include/pasture_amd.h) -----------------------------------------
@@ -1212,10 +1202,7 @@ def sample_kernel_shape(api=None) -> dict:
 def sample_phase_times(api=None):
     """(index build, decision rounds, mask write) in milliseconds of this thread's last poisson_disk_mask call; zeros unless
     PST_SAMPLE_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).sample_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "sample_phase_times", 3)
 
 
 # ---- gather by index and sort orders: attribute, Morton, shuffle (include/pasture_amd.h) ----------------------------------------------------
@@ -1316,7 +1303,4 @@ def reorder_kernel_shape(api=None) -> dict:
 def reorder_phase_times(api=None):
     """(bounds and keys, sort, gather) in milliseconds of this thread's last synchronous gather or sort-order call; zeros unless
     PST_REORDER_TIMES=1 was set when the library first ran one."""
-    from ._capi import product_api
-    ms = (C.c_double * 3)()
-    (api or product_api()).reorder_phase_times(ms)
-    return tuple(ms)
+    return _phase_times(api, "reorder_phase_times", 3)

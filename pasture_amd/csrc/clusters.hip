@@ -15,7 +15,7 @@
 //   number    size filter, flag the smallest member of every kept component, exclusive scan (= the kept roots in ascending smallest-member
 //             order), one stable sort on 0xFFFFFFFF - size (ties keep that order), ranks back to the roots, labels to the points.
 //
-// The grid's cell edge is STRICTLY larger than the tolerance, by the relative margin 2^-20 (clusters_api.cpp makes it, and doubles it until no
+// The grid's cell edge is STRICTLY larger than the tolerance, by the relative margin 2^-20 (cluster_grid.hpp makes it, and doubles it until no
 // axis has more than 2^21 - 1 cells).  Why that is enough for "adjacent points are at most one cell apart on every axis": adjacency gives
 // dx*dx <= t2 up to the roundings of the sum, so |xj - xi| <= tolerance * (1 + 2^-50).  The cell number is trunc(q), q = fl(fl(x - min) / edge):
 // two roundings, so q is within the relative error 2^-52 of the exact (x - min) / edge, which is below 2^21: an absolute error below 2^-31 each.

@@ -1,43 +1,17 @@
-// pst_euclidean_clusters / pst_cluster_mask_device / pst_cluster_kernel_shape: argument checks, the grid, the scratch layout and the order of the
-// launches of clusters.hip (where the definitions and the argument for the grid's margin are).
+// pst_euclidean_clusters / pst_cluster_mask_device / pst_cluster_kernel_shape: argument checks, the scratch layout and the order of the
+// launches of clusters.hip (where the definitions and the argument for the grid's margin are; the grid is cluster_grid.hpp's, the index build
+// cluster_index.hpp's).
 #include <cmath>
 #include <cstring>
-#include <utility>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
 namespace {
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
-
-// PST_CLUSTER_TIMES=1: stream events around the three phases of every call (tools/bench_clusters.py reads them through pst_cluster_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_CLUSTER_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_CLUSTER_TIMES=1 (tools/bench_clusters.py reads them through pst_cluster_phase_times)
 
 }  // namespace
 
@@ -79,17 +53,16 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   if (!std::isfinite(tolerance) || !(tolerance > 0.0) || !std::isnormal(t2))
     throw Error(PST_ERR_INVALID_ARGUMENT, who + ": tolerance must be finite and positive, and its square a normal number");
   if (min_size == 0 || min_size > max_size) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": min_size must be at least 1 and not above max_size");
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   ensure_device();
-  if (b->len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
+  check_point_count(b->len, who);
   *n_clusters = 0;
   *n_clustered = 0;
   const size_t n = b->len;
   if (n == 0) return PST_OK;  // no points, no clusters, no labels to write
 
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
+  const pstk::Positions pos = positions_of(*b, pm);
   const bool labels_on_device = labels_memkind == PST_MEM_DEVICE;
 
   // One block of scratch.  The sort's input pair and the sorted positions are dead once the traversal has run; the bookkeeping lives in them:
@@ -104,66 +77,50 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort32_bytes, nullptr, nullptr, nullptr, nullptr, n, 32, s));
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, n + 1, s));
   const size_t tmp_bytes = std::max(sort64_bytes, std::max(sort32_bytes, scan_bytes));
-  const size_t b4 = up256((n + 1) * 4), b8 = 2 * b4;  // an 8-byte array's room is exactly two 4-byte arrays' (the halves are used as such)
-  const auto halves = [b4](void* p) { return std::pair<uint32_t*, uint32_t*>{(uint32_t*)p, (uint32_t*)((uint8_t*)p + b4)}; };
   ScratchLayout layout;
-  const size_t off_keys_a = layout.add(b8), off_keys_b = layout.add(b8), off_vals_a = layout.add(b4), off_order = layout.add(b4);
-  const size_t off_xs = layout.add(b8), off_ys = layout.add(b8), off_zs = layout.add(b8), off_parent = layout.add(b4), off_offsets = layout.add(b8);
-  const size_t off_rec = layout.add(256), off_tmp = layout.add(tmp_bytes), off_labels = layout.add(labels_on_device ? 0 : b4);
+  ClusterIndex ix;
+  ix.carve(layout, n);
+  const size_t off_parent = layout.add(ix.b4), off_offsets = layout.add(2 * ix.b4);
+  const size_t off_rec = layout.add(256), off_tmp = layout.add(tmp_bytes), off_labels = layout.add(labels_on_device ? 0 : ix.b4);
   Scratch scratch(layout, s, who.c_str());
-  uint64_t* keys_a = scratch.at<uint64_t>(off_keys_a);
-  uint64_t* keys_b = scratch.at<uint64_t>(off_keys_b);
-  uint32_t* vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t* order = scratch.at<uint32_t>(off_order);
-  double* xs = scratch.at<double>(off_xs);
-  double* ys = scratch.at<double>(off_ys);
-  double* zs = scratch.at<double>(off_zs);
+  ix.bind(scratch);
   uint32_t* parent = scratch.at<uint32_t>(off_parent);
   unsigned long long* offsets = scratch.at<unsigned long long>(off_offsets);
   pstk::ClusterRecord* rec = scratch.at<pstk::ClusterRecord>(off_rec);
   void* tmp = scratch.at<void>(off_tmp);
   uint32_t* labels_dev = labels_on_device ? labels : scratch.at<uint32_t>(off_labels);
+  uint32_t* const order = ix.order;
 
-  PhaseEvents events;
+  static const bool timed = env_nonzero("PST_CLUSTER_TIMES");
+  PhaseEvents<3> events(timed, t_phase_ms);
   events.mark(0, s);
-  // ---- index build: AABB of the finite points -> (host: grid) -> keys -> sort -> gather
-  if (!pstk::cluster_bounds(pos, rec, s)) throw hip_failure("cluster bounds launch failed: ");
-  pstk::ClusterRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  const uint32_t nf = (uint32_t)r.finite_count;
+  // ---- index build: AABB of the finite points -> (host: grid) -> keys -> sort (the gather is the traversal launcher's)
+  const FiniteBounds bounds = finite_bounds(pos, rec, s, who);
+  const uint32_t nf = (uint32_t)bounds.count;
   if (nf == 0) {  // nothing but non-finite points: every label is "none"
-    if (labels_on_device) PST_HIP_CHECK(hipMemsetAsync(labels, 0xFF, n * sizeof(uint32_t), s));
-    else std::memset(labels, 0xFF, n * sizeof(uint32_t));
+    fill_result(labels, 0xFF, n * sizeof(uint32_t), labels_on_device, s);
     stream_sync(s);
     return PST_OK;
   }
-  double lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = pstk::cluster_decode_ordered(r.min_ordered[a]);
-    hi[a] = pstk::cluster_decode_ordered(r.max_ordered[a]);
-  }
-  const pstk::ClusterGrid grid = cluster_grid_over(lo, hi, tolerance, who);
-  const unsigned key_bits = grid.bits[0] + grid.bits[1] + grid.bits[2];
-  if (!pstk::cluster_keys(pos, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure("cluster key launch failed: ");
-  size_t bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::sort_pairs_u64(tmp, bytes, keys_a, keys_b, vals_a, order, n, key_bits + 1, s));
+  const pstk::ClusterGrid grid = cluster_grid_over(bounds, tolerance, who);
+  ix.build(pos, grid, nf, tmp, tmp_bytes, s, who, false);
   // ---- traversal + union
-  if (!pstk::cluster_components(pos, grid, t2, (const unsigned long long*)keys_b, order, nf, xs, ys, zs, parent, s, events.on ? events.e[1] : nullptr))
+  if (!pstk::cluster_components(pos, grid, t2, ix.sorted_keys(), order, nf, ix.xs, ix.ys, ix.zs, parent, s, events.event(1)))
     throw hip_failure("cluster traversal launch failed: ");
   events.mark(2, s);
   // ---- bookkeeping
-  const auto [root, size] = halves(xs);
-  const auto [min_index, root_at] = halves(ys);
-  uint32_t* flags = halves(zs).first;
-  const auto [list_keys, list_roots] = halves(keys_a);
-  const auto [sorted_keys, sorted_roots] = halves(keys_b);
-  uint32_t* rank_of_root = vals_a;
+  const auto [root, size] = ix.halves(ix.xs);
+  const auto [min_index, root_at] = ix.halves(ix.ys);
+  uint32_t* flags = ix.halves(ix.zs).first;
+  const auto [list_keys, list_roots] = ix.halves(ix.keys_a);
+  const auto [sorted_keys, sorted_roots] = ix.halves(ix.keys_b);
+  uint32_t* rank_of_root = ix.vals_a;
   if (!pstk::cluster_flag_kept(parent, order, n, nf, min_size, max_size, root, size, min_index, flags, root_at, rec, s)) throw hip_failure("cluster flatten launch failed: ");
-  bytes = tmp_bytes;
+  size_t bytes = tmp_bytes;
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, n + 1, s));
   if (!pstk::cluster_list_kept(flags, offsets, root_at, size, n, list_keys, list_roots, s)) throw hip_failure("cluster list launch failed: ");
   unsigned long long kept = 0;
+  pstk::ClusterRecord r{};  // (its `clustered`)
   PST_HIP_CHECK(hipMemcpyAsync(&kept, offsets + n, sizeof(kept), hipMemcpyDeviceToHost, s));
   PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
   stream_sync(s);

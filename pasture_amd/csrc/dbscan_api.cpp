@@ -1,44 +1,17 @@
-// pst_dbscan / pst_dbscan_kernel_shape / pst_dbscan_phase_times: argument checks, the grid, the scratch layout and the order of the launches
-// of dbscan.hip (where the pipeline is laid out; the definitions are in include/pasture_amd.h, the argument for the grid's margin at the head
-// of clusters.hip).
+// pst_dbscan / pst_dbscan_kernel_shape / pst_dbscan_phase_times: argument checks, the scratch layout and the order of the launches of
+// dbscan.hip (where the pipeline is laid out; the definitions are in include/pasture_amd.h, the argument for the grid's margin at the head
+// of clusters.hip; the grid is cluster_grid.hpp's, the index build cluster_index.hpp's).
 #include <cmath>
 #include <cstring>
-#include <utility>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
 namespace {
 
-thread_local double t_phase_ms[4] = {0.0, 0.0, 0.0, 0.0};
-
-// PST_DBSCAN_TIMES=1: stream events around the four phases of every call (tools/bench_dbscan.py reads them through pst_dbscan_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_DBSCAN_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
+thread_local double t_phase_ms[4] = {0.0, 0.0, 0.0, 0.0};  // PST_DBSCAN_TIMES=1 (tools/bench_dbscan.py reads them through pst_dbscan_phase_times)
 
 }  // namespace
 
@@ -67,16 +40,15 @@ int pst_dbscan(const pst_buffer* b, double eps, uint64_t min_points, uint32_t* l
   const double e2 = eps * eps;
   if (!std::isfinite(eps) || !(eps > 0.0) || !std::isnormal(e2)) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": eps must be finite and positive, and its square a normal number");
   if (min_points == 0) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": min_points must be at least 1");
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   ensure_device();
-  if (b->len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
+  check_point_count(b->len, who);
   counts[0] = counts[1] = counts[2] = 0;
   const size_t n = b->len;
   if (n == 0) return PST_OK;  // no points: no clusters, no label and no core byte to write
 
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
+  const pstk::Positions pos = positions_of(*b, pm);
   const bool on_device = memkind == PST_MEM_DEVICE;
 
   // One block of scratch, the clusters' plus n bytes of core flags.  The sort's input pair is dead once the sort has run, the sorted keys and
@@ -95,21 +67,16 @@ int pst_dbscan(const pst_buffer* b, double eps, uint64_t min_points, uint32_t* l
   PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort32_bytes, nullptr, nullptr, nullptr, nullptr, n, 32, s));
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, n + 1, s));
   const size_t tmp_bytes = std::max(sort64_bytes, std::max(sort32_bytes, scan_bytes));
-  const size_t b4 = up256((n + 1) * 4), b8 = 2 * b4;  // an 8-byte array's room is exactly two 4-byte arrays' (the halves are used as such)
-  const auto halves = [b4](void* p) { return std::pair<uint32_t*, uint32_t*>{(uint32_t*)p, (uint32_t*)((uint8_t*)p + b4)}; };
   ScratchLayout layout;
-  const size_t off_keys_a = layout.add(b8), off_keys_b = layout.add(b8), off_vals_a = layout.add(b4), off_order = layout.add(b4);
-  const size_t off_xs = layout.add(b8), off_ys = layout.add(b8), off_zs = layout.add(b8), off_parent = layout.add(b4), off_core = layout.add(n);
-  const size_t off_offsets = layout.add(b8), off_rec = layout.add(256), off_counts = layout.add(256), off_tmp = layout.add(tmp_bytes);
-  const size_t off_labels = layout.add(on_device ? 0 : b4), off_core_out = layout.add(on_device || !core ? 0 : n);
+  ClusterIndex ix;
+  ix.carve(layout, n);
+  const size_t off_parent = layout.add(ix.b4), off_core = layout.add(n);
+  const size_t off_offsets = layout.add(2 * ix.b4), off_rec = layout.add(256), off_counts = layout.add(256), off_tmp = layout.add(tmp_bytes);
+  const size_t off_labels = layout.add(on_device ? 0 : ix.b4), off_core_out = layout.add(on_device || !core ? 0 : n);
   Scratch scratch(layout, s, who.c_str());
-  uint64_t* keys_a = scratch.at<uint64_t>(off_keys_a);
-  uint64_t* keys_b = scratch.at<uint64_t>(off_keys_b);
-  uint32_t* vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t* order = scratch.at<uint32_t>(off_order);
-  double* xs = scratch.at<double>(off_xs);
-  double* ys = scratch.at<double>(off_ys);
-  double* zs = scratch.at<double>(off_zs);
+  ix.bind(scratch);
+  uint32_t* const order = ix.order;
+  double *const xs = ix.xs, *const ys = ix.ys, *const zs = ix.zs;
   uint32_t* parent = scratch.at<uint32_t>(off_parent);
   uint8_t* core_sorted = scratch.at<uint8_t>(off_core);
   unsigned long long* offsets = scratch.at<unsigned long long>(off_offsets);
@@ -119,55 +86,39 @@ int pst_dbscan(const pst_buffer* b, double eps, uint64_t min_points, uint32_t* l
   uint32_t* labels_dev = on_device ? labels : scratch.at<uint32_t>(off_labels);
   uint8_t* core_dev = !core ? nullptr : on_device ? core : scratch.at<uint8_t>(off_core_out);
 
-  PhaseEvents events;
+  static const bool timed = env_nonzero("PST_DBSCAN_TIMES");
+  PhaseEvents<4> events(timed, t_phase_ms);
   events.mark(0, s);
   // ---- index build: AABB of the finite points -> (host: grid) -> keys -> sort -> gather
-  if (!pstk::cluster_bounds(pos, rec, s)) throw hip_failure(who + ": bounds launch failed: ");
-  pstk::ClusterRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  const uint32_t nf = (uint32_t)r.finite_count;
+  const FiniteBounds bounds = finite_bounds(pos, rec, s, who);
+  const uint32_t nf = (uint32_t)bounds.count;
   if (nf == 0 || min_points > nf) {  // no point can have min_points neighbours: everything is noise
-    if (on_device) {
-      PST_HIP_CHECK(hipMemsetAsync(labels, 0xFF, n * sizeof(uint32_t), s));
-      if (core) PST_HIP_CHECK(hipMemsetAsync(core, 0, n, s));
-    } else {
-      std::memset(labels, 0xFF, n * sizeof(uint32_t));
-      if (core) std::memset(core, 0, n);
-    }
+    fill_result(labels, 0xFF, n * sizeof(uint32_t), on_device, s);
+    if (core) fill_result(core, 0, n, on_device, s);
     stream_sync(s);
     return PST_OK;
   }
-  double lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) {
-    lo[a] = pstk::cluster_decode_ordered(r.min_ordered[a]);
-    hi[a] = pstk::cluster_decode_ordered(r.max_ordered[a]);
-  }
-  const pstk::ClusterGrid grid = cluster_grid_over(lo, hi, eps, who);
-  const unsigned key_bits = grid.bits[0] + grid.bits[1] + grid.bits[2];
-  if (!pstk::cluster_keys(pos, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure(who + ": key launch failed: ");
-  size_t bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::sort_pairs_u64(tmp, bytes, keys_a, keys_b, vals_a, order, n, key_bits + 1, s));
-  if (!pstk::nn_gather(pos, order, nf, xs, ys, zs, s)) throw hip_failure(who + ": gather launch failed: ");
+  const pstk::ClusterGrid grid = cluster_grid_over(bounds, eps, who);
+  ix.build(pos, grid, nf, tmp, tmp_bytes, s, who, true);
   PST_HIP_CHECK(hipMemsetAsync(counts_dev, 0, 2 * sizeof(*counts_dev), s));
   events.mark(1, s);
   // ---- core points
-  const unsigned long long* keys = (const unsigned long long*)keys_b;
+  const unsigned long long* keys = ix.sorted_keys();
   if (!pstk::dbscan_count(keys, xs, ys, zs, nf, grid, e2, (uint32_t)min_points, core_sorted, parent, counts_dev, s)) throw hip_failure(who + ": count launch failed: ");
   events.mark(2, s);
   // ---- clusters of the core points
   if (!pstk::dbscan_link(keys, xs, ys, zs, core_sorted, nf, grid, e2, parent, s)) throw hip_failure(who + ": link launch failed: ");
   events.mark(3, s);
   // ---- border points, then the bookkeeping
-  uint32_t* root = vals_a;
-  const auto [size, min_index] = halves(keys_a);
+  uint32_t* root = ix.vals_a;
+  const auto [size, min_index] = ix.halves(ix.keys_a);
   if (!pstk::dbscan_border(keys, xs, ys, zs, core_sorted, order, nf, grid, e2, parent, root, size, min_index, s)) throw hip_failure(who + ": border launch failed: ");
-  const auto [list_keys, list_roots] = halves(xs);
-  const auto [sorted_keys, sorted_roots] = halves(keys_b);
-  uint32_t* rank_of_root = halves(ys).first;
-  const auto [root_at, flags] = halves(zs);
+  const auto [list_keys, list_roots] = ix.halves(xs);
+  const auto [sorted_keys, sorted_roots] = ix.halves(ix.keys_b);
+  uint32_t* rank_of_root = ix.halves(ys).first;
+  const auto [root_at, flags] = ix.halves(zs);
   if (!pstk::dbscan_flag(root, size, min_index, n, nf, flags, root_at, counts_dev + 1, s)) throw hip_failure(who + ": flag launch failed: ");
-  bytes = tmp_bytes;
+  size_t bytes = tmp_bytes;
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, n + 1, s));
   if (!pstk::cluster_list_kept(flags, offsets, root_at, size, n, list_keys, list_roots, s)) throw hip_failure(who + ": list launch failed: ");
   unsigned long long clusters = 0, counted[2] = {0, 0};

@@ -35,12 +35,11 @@ int pst_geometric_features_from_knn_device(const pst_buffer* b, size_t k, const 
   not_null(d_knn, "d_knn");
   if (k < 1 || k > 64) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": k must be between 1 and 64");
   check_feature_args(max_distance, features, d_out, d_normals, d_directions, who);
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   if (b->len == 0) return PST_OK;
   ensure_device();
-  if (b->len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
-  if (!pstk::geometric_features(positions_of(*b, *pm), (uint32_t)k, d_knn, max_distance, features, d_out, d_normals, d_directions, current_stream()))
+  check_point_count(b->len, who);
+  if (!pstk::geometric_features(positions_of(*b, pm), (uint32_t)k, d_knn, max_distance, features, d_out, d_normals, d_directions, current_stream()))
     throw hip_failure("geometric features launch failed: ");
   PST_API_END
 }

@@ -3,60 +3,14 @@
 #include <cmath>
 #include <cstring>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
 namespace {
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
-
-// PST_HAG_TIMES=1: stream events around the three phases of every call (tools/bench_hag.py reads them through pst_hag_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_HAG_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
-
-const Member& position_member(const pst_buffer& b) {
-  const Member* m = position_vec3f64(b);
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
-  return *m;
-}
-
-// the masked bounds of G, read back (two launches, one synchronisation).  Their block partials are needed before the grid -- and with it the
-// size of the call's scratch -- is known: they live in a small block of their own, like the bounds record of pmf_api.cpp.
-pstk::HagBounds ground_bounds(const pstk::Positions& ground, const uint8_t* mask, hipStream_t s, const char* who) {
-  ScratchLayout layout;
-  const size_t off_partials = layout.add(pstk::hag_bounds_partials_bytes(ground.n)), off_rec = layout.add(sizeof(pstk::HagBounds));
-  Scratch block(layout, s, who);
-  pstk::HagBounds* rec = block.at<pstk::HagBounds>(off_rec);
-  if (!pstk::hag_bounds(ground, mask, block.at<void>(off_partials), rec, s)) throw hip_failure(std::string(who) + ": bounds launch failed: ");
-  pstk::HagBounds r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  return r;
-}
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_HAG_TIMES=1 (tools/bench_hag.py reads them through pst_hag_phase_times)
 
 }  // namespace
 
@@ -95,14 +49,16 @@ int pst_height_above_ground_device(const pst_buffer* query, const pst_buffer* gr
   const size_t nq = query->len, ng_points = ground->len;
   if (nq == 0) return PST_OK;  // no query: nothing to write
   ensure_device();
-  if (nq >= 0xFFFFFFF0ull || ng_points >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+  check_point_count(nq, who);
+  check_point_count(ng_points, who);
 
   hipStream_t s = current_stream();
   const pstk::Positions qpos = positions_of(*query, qm), gpos = positions_of(*ground, gm);
-  PhaseEvents events;
+  static const bool timed = env_nonzero("PST_HAG_TIMES");
+  PhaseEvents<3> events(timed, t_phase_ms);
   events.mark(0, s);
   pstk::HagBounds bounds{};
-  if (ng_points) bounds = ground_bounds(gpos, d_ground_mask, s, who);
+  if (ng_points) bounds = finite_bounds_2d(gpos, d_ground_mask, s, who);  // of G
   const uint32_t ng = (uint32_t)bounds.count;
   unsigned long long unresolved = 0;
 
@@ -180,12 +136,11 @@ int pst_buffer_u8_equals_mask_device(const pst_buffer* b, const char* attribute_
   PST_API_BEGIN
   not_null(b, "buffer");
   not_null(attribute_name, "attribute_name");
-  const Member* m = b->layout.find(AttributeDef{attribute_name, DataType{}});  // (a default datatype is U8)
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& m = required(b->layout.find(AttributeDef{attribute_name, DataType{}}));  // (a default datatype is U8)
   if (b->len == 0) return PST_OK;
   not_null(d_mask, "d_mask");
   ensure_device();
-  const AttrView v = attr_view(*b, m);
+  const AttrView v = attr_view(*b, &m);
   if (!pstk::u8_equals_mask(v.addr, v.stride, b->len, value, d_mask, current_stream())) throw hip_failure("equals-mask launch failed: ");
   PST_API_END
 }

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/pasture_amd.h"
+#include "cluster_grid.hpp"
 #include "hag_grid.hpp"
 #include "plan.h"
 
@@ -226,8 +227,7 @@ constexpr uint32_t kClusterTilePoints = 0;        // points of an LDS candidate 
 // points that carry a label
 struct ClusterRecord { unsigned long long min_ordered[3], max_ordered[3], finite_count, clustered; };
 double cluster_decode_ordered(unsigned long long v);
-// cell = trunc((v - min) / edge) per axis, dim cells and `bits` key bits per axis (x lowest); every key is below 2^(bits[0] + bits[1] + bits[2])
-struct ClusterGrid { double min[3]; double edge; uint32_t dim[3]; uint32_t bits[3]; };
+// (ClusterGrid: cluster_grid.hpp)
 bool cluster_bounds(const Positions& pos, ClusterRecord* rec, hipStream_t stream);
 // keys[i] = cell key of point i (all ones: not finite), vals[i] = i
 bool cluster_keys(const Positions& pos, const ClusterGrid& g, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
@@ -378,8 +378,8 @@ bool raster_reduce_heavy(const double* sorted_values, const uint32_t* dir, uint3
 // square of h cells around them (the canonical NaN without one); h <= kRasterFillMaxHalfWidth
 bool raster_grid_fill(const double* in, double* out, uint32_t cols, uint32_t rows, uint32_t h, hipStream_t stream);
 
-// Minimum-distance (Poisson-disk) subsampling (sample.hip; the checks, the scratch and the loop of rounds are in sample_api.cpp).  The index is
-// the cluster index: cluster_keys on a ClusterGrid, the 64-bit sort, nn_gather.  The seams (pst_sample_kernel_shape):
+// Minimum-distance (Poisson-disk) subsampling (sample.hip; the checks, the scratch and the loop of rounds are in sample_api.cpp; the index is
+// cluster_index.hpp's).  The seams (pst_sample_kernel_shape):
 constexpr uint32_t kSamplePointsPerBlock = 256;         // active points one workgroup of the decision kernel owns, one lane each
 constexpr uint32_t kSampleSweepsPerLaunch = 2;          // times a lane looks at its point in one launch before it leaves it undecided
 constexpr uint32_t kSampleBoundsPointsPerBlock = 4096;  // points per block partial of the bounds, sixteen per lane
@@ -398,8 +398,8 @@ bool sample_compact(const uint32_t* active, const uint32_t* flags, const unsigne
 // mask[order[s]] = 1 iff s < nf and state[s] is "kept", else 0, for all n sorted positions; *kept (zeroed) += the ones, one integer atomic per workgroup
 bool sample_mask(const uint32_t* order, const uint8_t* state, uint64_t n, uint32_t nf, uint8_t* mask, unsigned long long* kept, hipStream_t stream);
 
-// DBSCAN (dbscan.hip; the checks, the scratch and the order of the launches are in dbscan_api.cpp).  The index is the cluster index:
-// cluster_bounds, cluster_keys on a ClusterGrid, the 64-bit sort, nn_gather.  The seam (pst_dbscan_kernel_shape):
+// DBSCAN (dbscan.hip; the checks, the scratch and the order of the launches are in dbscan_api.cpp; the index is
+// cluster_index.hpp's).  The seam (pst_dbscan_kernel_shape):
 constexpr uint32_t kDbscanPointsPerBlock = 256;  // points one workgroup of the count, link and border kernels owns, one lane each
 // core[s] = 1 iff sorted point s has at least min_points neighbours, itself included (1 <= min_points <= nf); parent[s] = s; *n_core (zeroed) +=
 // the core points, one integer atomic per wave

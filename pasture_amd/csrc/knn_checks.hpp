@@ -10,14 +10,12 @@ namespace pst {
 inline const Member& knn_checked_arguments(const pst_buffer& b, size_t k, const char* who) {
   if (k < 3) throw Error(PST_ERR_K_TOO_SMALL, "The k nearest neigbors attribute is too small!");
   if (k > 64) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": k > 64 is not supported by the register-resident k-best list");
-  const Member* m = position_vec3f64(b);
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
-  return *m;
+  return position_member(b);
 }
 inline void knn_checked_length(const pst_buffer& b, size_t at_least, const char* who) {
   if (b.len < 3) throw Error(PST_ERR_TOO_FEW_POINTS, "The point cloud is too small. Please use a point cloud that has 3 or more points!");
   if (b.len < at_least) throw Error(PST_ERR_TOO_FEW_POINTS, std::string(who) + ": the point cloud needs at least " + std::to_string(at_least) + " points");
-  if (b.len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+  check_point_count(b.len, who);
 }
 
 // the neighbour lists only; degenerate plane fits (a positive return) are no error here: the lists are written whatever the fit says

@@ -4,10 +4,10 @@
 #include <cmath>
 #include <cstring>
 
-#include "device_sort.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 #include "plane_solve.hpp"
 #include "rigid_solve.hpp"
-#include "runtime.hpp"
 
 using namespace pst;
 
@@ -43,34 +43,23 @@ struct pst_nn_index {
 
 namespace {
 
-constexpr uint32_t kMaxCellsPerAxis = (1u << 21) - 1;  // the cluster grid's key layout: 21 bits per axis
 // automatic edge: the mean number of targets per OCCUPIED cell is brought into [kMeanLow, kMeanHigh], aiming at kMeanAim
 constexpr double kMeanLow = 2.0, kMeanHigh = 16.0, kMeanAim = 6.0;
 constexpr double kStopMargin = 0x1p-20;  // edge_stop = edge * (1 - 2^-20), the margin of the ring bound (nn.hip)
 
-uint32_t bits_for(uint32_t cells) {
-  uint32_t b = 0;
-  while ((1ull << b) < cells) ++b;
-  return b;
-}
-
-// the grid of clusters_api.cpp for a given edge: doubled until no axis needs more than 2^21 - 1 cells
-pstk::NnGrid make_grid(const pstk::ClusterRecord& r, double edge) {
+// the cluster grid (cluster_grid.hpp) for a given edge, written to *cells for the key kernel; returned with the far corner and the ring
+// bound's edge for the searches
+pstk::NnGrid make_grid(const FiniteBounds& b, double edge, pstk::ClusterGrid* cells) {
+  if (!pstk::cluster_grid_for_edge(b.min, b.max, edge, cells)) throw Error(PST_ERR_UNSUPPORTED, "pst_nn_index_create: the extent of the finite points overflows f64");
   pstk::NnGrid g{};
-  double extent[3];
   for (int a = 0; a < 3; ++a) {
-    g.min[a] = pstk::cluster_decode_ordered(r.min_ordered[a]);
-    g.max[a] = pstk::cluster_decode_ordered(r.max_ordered[a]);
-    extent[a] = g.max[a] - g.min[a];
-    if (!std::isfinite(extent[a])) throw Error(PST_ERR_UNSUPPORTED, "pst_nn_index_create: the extent of the finite points overflows f64");
+    g.min[a] = cells->min[a];
+    g.max[a] = b.max[a];
+    g.dim[a] = cells->dim[a];
+    g.bits[a] = cells->bits[a];
   }
-  g.edge = edge;
-  while (extent[0] / g.edge >= (double)kMaxCellsPerAxis || extent[1] / g.edge >= (double)kMaxCellsPerAxis || extent[2] / g.edge >= (double)kMaxCellsPerAxis) g.edge *= 2.0;
+  g.edge = cells->edge;
   g.edge_stop = g.edge * (1.0 - kStopMargin);
-  for (int a = 0; a < 3; ++a) {
-    g.dim[a] = (uint32_t)(extent[a] / g.edge) + 1;
-    g.bits[a] = bits_for(g.dim[a]);
-  }
   return g;
 }
 
@@ -78,11 +67,11 @@ pstk::NnGrid make_grid(const pstk::ClusterRecord& r, double edge) {
 // out holds one layer of cells whatever the edge: it is taken out and the guess repeated over the remaining axes (a slab is gridded as a
 // rectangle, a rod as a line).  A sheet that is not axis-parallel still fills a small share of its box, which only the count of occupied
 // cells after the sort can tell.
-double first_edge(const pstk::ClusterRecord& r) {
+double first_edge(const FiniteBounds& b) {
   double extent[3], longest = 0.0;
   bool active[3];
   for (int a = 0; a < 3; ++a) {
-    extent[a] = pstk::cluster_decode_ordered(r.max_ordered[a]) - pstk::cluster_decode_ordered(r.min_ordered[a]);
+    extent[a] = b.max[a] - b.min[a];
     active[a] = extent[a] > 0.0 && std::isfinite(extent[a]);
     if (active[a]) longest = std::fmax(longest, extent[a]);
   }
@@ -93,7 +82,7 @@ double first_edge(const pstk::ClusterRecord& r) {
     for (int a = 0; a < 3; ++a)
       if (active[a]) { log_volume += std::log(extent[a]); ++axes; }
     if (axes == 0) break;
-    edge = std::exp((log_volume + std::log(kMeanAim / (double)r.finite_count)) / axes);  // (logarithms: the product of the extents may overflow)
+    edge = std::exp((log_volume + std::log(kMeanAim / (double)b.count)) / axes);  // (logarithms: the product of the extents may overflow)
     bool dropped = false;
     for (int a = 0; a < 3; ++a)
       if (active[a] && extent[a] < edge && extent[a] < longest) { active[a] = false; dropped = true; }
@@ -115,48 +104,17 @@ struct CheckedTransform {
   }
 };
 
-const Member& position_member(const pst_buffer& b) {
-  const Member* m = position_vec3f64(b);
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
-  return *m;
+thread_local double t_phase_ms[2] = {0.0, 0.0};  // PST_NN_TIMES=1 (tools/bench_nn.py reads them through pst_nn_phase_times)
+
+bool times_wanted() {
+  static const bool wanted = env_nonzero("PST_NN_TIMES");
+  return wanted;
 }
-
-void checked_length(const pst_buffer& b, const char* who) {
-  if (b.len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
-}
-
-thread_local double t_phase_ms[2] = {0.0, 0.0};
-
-// PST_NN_TIMES=1: stream events around the two phases of every search (tools/bench_nn.py reads them through pst_nn_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_NN_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 2; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
 
 // The search of one query cloud: keys -> sort -> search, in one block of scratch that lives until the caller has synchronised.
 struct Search {
   Scratch scratch;
-  PhaseEvents events;
+  PhaseEvents<2> events{times_wanted(), t_phase_ms};
   uint32_t* at = nullptr;  // with_at: position of every query's match in the index's sorted arrays
   void run(const pst_nn_index& ix, const pstk::Positions& pos, const pstk::NnTransform& t, double m2, uint32_t* d_idx, double* d_dist, bool with_at, size_t extra_bytes,
            size_t* extra_offset, hipStream_t s, const char* who) {
@@ -310,7 +268,7 @@ int pst_nn_index_create(const pst_buffer* target, double cell_edge, pst_nn_index
   if (!(cell_edge >= 0.0) || std::isinf(cell_edge)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": cell_edge must be finite and not negative (0: automatic)");
   const Member& pm = position_member(*target);
   ensure_device();
-  checked_length(*target, who);
+  check_point_count(target->len, who);
   std::unique_ptr<pst_nn_index> ix(new pst_nn_index);
   const size_t n = target->len;
   ix->n_target = n;
@@ -334,11 +292,8 @@ int pst_nn_index_create(const pst_buffer* target, double cell_edge, pst_nn_index
   pstk::ClusterRecord* rec = scratch.at<pstk::ClusterRecord>(off_rec);
   unsigned long long* count = scratch.at<unsigned long long>(off_count);
 
-  if (!pstk::cluster_bounds(pos, rec, s)) throw hip_failure(std::string(who) + ": bounds launch failed: ");
-  pstk::ClusterRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  const uint32_t nf = (uint32_t)r.finite_count;
+  const FiniteBounds bounds = finite_bounds(pos, rec, s, who);
+  const uint32_t nf = (uint32_t)bounds.count;
   if (nf == 0) {  // no finite target
     *out = ix.release();
     return PST_OK;
@@ -347,14 +302,12 @@ int pst_nn_index_create(const pst_buffer* target, double cell_edge, pst_nn_index
   // occupancy goes with edge^d, d the cloud's local dimension: 2 is assumed for the first correction (sheets are what the box volume gets
   // wrong), the second one takes d from the two measurements.
   pstk::NnGrid grid{};
-  double edge = cell_edge > 0.0 ? cell_edge : first_edge(r), prev_edge = 0.0, prev_mean = 0.0;
+  double edge = cell_edge > 0.0 ? cell_edge : first_edge(bounds), prev_edge = 0.0, prev_mean = 0.0;
   unsigned long long occupied = 0;
   for (int round = 0;; ++round) {
-    grid = make_grid(r, edge);
-    const pstk::ClusterGrid cg{{grid.min[0], grid.min[1], grid.min[2]}, grid.edge, {grid.dim[0], grid.dim[1], grid.dim[2]}, {grid.bits[0], grid.bits[1], grid.bits[2]}};
-    if (!pstk::cluster_keys(pos, cg, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
-    size_t bytes = sort_bytes;
-    PST_HIP_CHECK(pstk::sort_pairs_u64(scratch.at<void>(off_tmp), bytes, keys_a, keys_b, vals_a, order, n, grid.bits[0] + grid.bits[1] + grid.bits[2] + 1, s));
+    pstk::ClusterGrid cells{};
+    grid = make_grid(bounds, edge, &cells);
+    cluster_sorted_keys(pos, cells, keys_a, keys_b, vals_a, order, scratch.at<void>(off_tmp), sort_bytes, s, who);
     if (!pstk::nn_count_cells((const unsigned long long*)keys_b, nf, count, s)) throw hip_failure(std::string(who) + ": cell count launch failed: ");
     PST_HIP_CHECK(hipMemcpyAsync(&occupied, count, sizeof(occupied), hipMemcpyDeviceToHost, s));
     stream_sync(s);
@@ -418,7 +371,7 @@ int pst_nearest_neighbours_device(const pst_nn_index* index, const pst_buffer* q
   const CheckedTransform t(transform12, who);
   const Member& pm = position_member(*query);
   ensure_device();
-  checked_length(*query, who);
+  check_point_count(query->len, who);
   if (query->len == 0) return PST_OK;
   hipStream_t s = current_stream();
   Search search;
@@ -450,7 +403,7 @@ int pst_icp_step(const pst_nn_index* index, const pst_buffer* source, const doub
   const CheckedTransform t(T_in, who);
   const Member& pm = position_member(*source);
   ensure_device();
-  checked_length(*source, who);
+  check_point_count(source->len, who);
   double out[12];
   icp_step(*index, positions_of(*source, pm), t.t.m, m2, sums, out, current_stream(), who);
   std::memcpy(T_out, out, sizeof(out));  // (T_out may be T_in)
@@ -470,7 +423,7 @@ int pst_icp(const pst_nn_index* index, const pst_buffer* source, const double* T
   if (!(rms_tolerance >= 0.0)) throw Error(PST_ERR_INVALID_ARGUMENT, std::string(who) + ": rms_tolerance must not be negative");
   const Member& pm = position_member(*source);
   ensure_device();
-  checked_length(*source, who);
+  check_point_count(source->len, who);
   const pstk::Positions pos = positions_of(*source, pm);
   double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, next[12], sums[17];
   if (T_init) std::memcpy(T, T_init, sizeof(T));
@@ -545,7 +498,7 @@ int pst_icp_plane_step(const pst_nn_index* index, const pst_buffer* source, cons
   const Member& pm = position_member(*source);
   require_normals(*index, who);
   ensure_device();
-  checked_length(*source, who);
+  check_point_count(source->len, who);
   double out[12];
   icp_plane_step(*index, positions_of(*source, pm), t.t.m, m2, sums, out, current_stream(), who);
   std::memcpy(T_out, out, sizeof(out));  // (T_out may be T_in)
@@ -566,7 +519,7 @@ int pst_icp_plane(const pst_nn_index* index, const pst_buffer* source, const dou
   const Member& pm = position_member(*source);
   require_normals(*index, who);
   ensure_device();
-  checked_length(*source, who);
+  check_point_count(source->len, who);
   const pstk::Positions pos = positions_of(*source, pm);
   double T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, next[12], sums[35];
   if (T_init) std::memcpy(T, T_init, sizeof(T));

@@ -4,7 +4,8 @@
 #include <cmath>
 #include <cstring>
 
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
@@ -50,20 +51,12 @@ Schedule make_schedule(const Params& p, const std::string& who) {
 }
 
 // the raster over the finite points' AABB: dim = cell of the largest coordinate + 1, by the expression pmf.hip evaluates per point
-pstk::PmfGrid make_grid(const pstk::ClusterRecord& r, double cell, const std::string& who) {
-  return pmf_grid_over(pstk::cluster_decode_ordered(r.min_ordered[0]), pstk::cluster_decode_ordered(r.min_ordered[1]), pstk::cluster_decode_ordered(r.max_ordered[0]),
-                       pstk::cluster_decode_ordered(r.max_ordered[1]), cell, who);
-}
+pstk::PmfGrid make_grid(const FiniteBounds& b, double cell, const std::string& who) { return pmf_grid_over(b.min[0], b.min[1], b.max[0], b.max[1], cell, who); }
 
-// the AABB record of the finite points, read back (one launch, one synchronisation)
-pstk::ClusterRecord finite_bounds(const pstk::Positions& pos, hipStream_t s, const std::string& who) {
+// the AABB of the finite points, read back through a small block of its own: the size of the call's scratch depends on it
+FiniteBounds finite_bounds(const pstk::Positions& pos, hipStream_t s, const std::string& who) {
   Scratch block;
-  pstk::ClusterRecord* rec = block.alloc<pstk::ClusterRecord>(256, s, who.c_str());
-  if (!pstk::cluster_bounds(pos, rec, s)) throw hip_failure(who + ": bounds launch failed: ");
-  pstk::ClusterRecord r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  return r;
+  return pst::finite_bounds(pos, block.alloc<pstk::ClusterRecord>(256, s, who.c_str()), s, who);
 }
 
 // A run of passes.  erode / dilate by h = the passes along the columns, then those along the rows; along an axis of d cells a half-width
@@ -97,33 +90,7 @@ struct Passes {
   }
 };
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
-
-// PST_PMF_TIMES=1: stream events around the three phases of every call (tools/bench_ground.py reads them through pst_pmf_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_PMF_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_PMF_TIMES=1 (tools/bench_ground.py reads them through pst_pmf_phase_times)
 
 }  // namespace
 
@@ -165,22 +132,21 @@ int pst_pmf_grid(const pst_buffer* b, double cell_size, double origin[2], uint32
   not_null(dim, "dim");
   not_null(n_finite, "n_finite");
   if (!std::isfinite(cell_size) || !(cell_size > 0.0)) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": cell_size must be finite and positive");
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   origin[0] = origin[1] = 0.0;
   dim[0] = dim[1] = 0;
   *n_finite = 0;
   if (b->len == 0) return PST_OK;
   ensure_device();
-  if (b->len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
-  const pstk::ClusterRecord r = finite_bounds(positions_of(*b, *pm), current_stream(), who);
-  if (r.finite_count == 0) return PST_OK;
+  check_point_count(b->len, who);
+  const FiniteBounds r = finite_bounds(positions_of(*b, pm), current_stream(), who);
+  if (r.count == 0) return PST_OK;
   const pstk::PmfGrid g = make_grid(r, cell_size, who);
   origin[0] = g.x0;
   origin[1] = g.y0;
   dim[0] = g.cols;
   dim[1] = g.rows;
-  *n_finite = r.finite_count;
+  *n_finite = r.count;
   PST_API_END
 }
 
@@ -194,23 +160,22 @@ int pst_pmf_ground_mask(const pst_buffer* b, double cell_size, double max_window
   if (mask_memkind > PST_MEM_PINNED_HOST) throw Error(PST_ERR_INVALID_ARGUMENT, "invalid mask memory kind");
   if (surfaces_memkind > PST_MEM_PINNED_HOST) throw Error(PST_ERR_INVALID_ARGUMENT, "invalid surfaces memory kind");
   const Schedule sched = make_schedule(Params{cell_size, max_window_size, slope, initial_distance, max_distance, exponential, base}, who);
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   *n_ground = 0;
   const size_t n = b->len;
   if (n == 0) return PST_OK;  // no points: no raster, no ground, no byte to write
   ensure_device();
-  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
+  check_point_count(n, who);
 
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
+  const pstk::Positions pos = positions_of(*b, pm);
   const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
-  PhaseEvents events;
+  static const bool timed = env_nonzero("PST_PMF_TIMES");
+  PhaseEvents<3> events(timed, t_phase_ms);
   events.mark(0, s);
-  const pstk::ClusterRecord r = finite_bounds(pos, s, who);
-  if (r.finite_count == 0) {  // nothing but non-finite points: no raster, no ground
-    if (mask_on_device) PST_HIP_CHECK(hipMemsetAsync(mask, 0, n, s));
-    else std::memset(mask, 0, n);
+  const FiniteBounds r = finite_bounds(pos, s, who);
+  if (r.count == 0) {  // nothing but non-finite points: no raster, no ground
+    fill_result(mask, 0, n, mask_on_device, s);
     stream_sync(s);
     return PST_OK;
   }
@@ -282,12 +247,11 @@ int pst_grid_morphology_device(const double* d_in, double* d_out, uint32_t cols,
 int pst_finite_mask_device(const pst_buffer* b, uint8_t* d_mask) {
   PST_API_BEGIN
   not_null(b, "buffer");
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   if (b->len == 0) return PST_OK;
   not_null(d_mask, "d_mask");
   ensure_device();
-  if (!pstk::finite_mask(positions_of(*b, *pm), d_mask, current_stream())) throw hip_failure("finite mask launch failed: ");
+  if (!pstk::finite_mask(positions_of(*b, pm), d_mask, current_stream())) throw hip_failure("finite mask launch failed: ");
   PST_API_END
 }
 
@@ -295,12 +259,11 @@ int pst_buffer_set_u8_where_device(pst_buffer* b, const char* attribute_name, co
   PST_API_BEGIN
   not_null(b, "buffer");
   not_null(attribute_name, "attribute_name");
-  const Member* m = b->layout.find(AttributeDef{attribute_name, DataType{}});  // (a default datatype is U8)
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& m = required(b->layout.find(AttributeDef{attribute_name, DataType{}}));  // (a default datatype is U8)
   if (b->len == 0) return PST_OK;
   not_null(d_mask, "d_mask");
   ensure_device();
-  const AttrView v = attr_view(*b, m);
+  const AttrView v = attr_view(*b, &m);
   if (!pstk::set_u8_where(v.addr, v.stride, b->len, d_mask, value, current_stream())) throw hip_failure("set-where launch failed: ");
   PST_API_END
 }

@@ -3,8 +3,8 @@
 #include <cmath>
 #include <cstring>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
@@ -12,46 +12,7 @@ namespace {
 
 constexpr uint64_t kMaxCells = 1ull << 28;
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
-
-// PST_RASTER_TIMES=1: stream events around the three phases of every call (tools/bench_raster.py reads them through pst_raster_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_RASTER_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
-
-// the bounds of the points with three finite components, whatever the mask says: hag.hip's block partials and one folding workgroup, no atomics
-pstk::HagBounds finite_bounds_2d(const pstk::Positions& pos, hipStream_t s, const char* who) {
-  ScratchLayout layout;
-  const size_t off_partials = layout.add(pstk::hag_bounds_partials_bytes(pos.n)), off_rec = layout.add(sizeof(pstk::HagBounds));
-  Scratch block(layout, s, who);
-  pstk::HagBounds* rec = block.at<pstk::HagBounds>(off_rec);
-  if (!pstk::hag_bounds(pos, nullptr, block.at<void>(off_partials), rec, s)) throw hip_failure(std::string(who) + ": bounds launch failed: ");
-  pstk::HagBounds r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  return r;
-}
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_RASTER_TIMES=1 (tools/bench_raster.py reads them through pst_raster_phase_times)
 
 // one plane per set bit of `stats`, in ascending bit order, rows x cols doubles each from `base`
 pstk::RasterPlanes planes_at(double* base, uint32_t stats, size_t cells) {
@@ -101,8 +62,7 @@ int pst_rasterize(const pst_buffer* b, const double* d_values, const uint8_t* d_
     if ((uint64_t)dim[0] * dim[1] > kMaxCells) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": the raster would have more than 2^28 cells: use a larger cell_size");
     grid = pstk::PmfGrid{origin[0], origin[1], cell_size, dim[0], dim[1]};
   }
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   *n_members = 0;
   const auto report = [&](const pstk::PmfGrid& g) {
     if (origin_out) { origin_out[0] = g.x0; origin_out[1] = g.y0; }
@@ -112,14 +72,15 @@ int pst_rasterize(const pst_buffer* b, const double* d_values, const uint8_t* d_
   const size_t n = b->len;
   if (n == 0 && !given) return PST_OK;  // no points, no grid: nothing to write
   ensure_device();
-  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 17 points per call");
+  check_point_count(n, who);
 
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
-  PhaseEvents events;
+  const pstk::Positions pos = positions_of(*b, pm);
+  static const bool timed = env_nonzero("PST_RASTER_TIMES");
+  PhaseEvents<3> events(timed, t_phase_ms);
   events.mark(0, s);
   if (!given) {
-    const pstk::HagBounds r = finite_bounds_2d(pos, s, who);
+    const pstk::HagBounds r = finite_bounds_2d(pos, nullptr, s, who);  // of the finite points, whatever the mask says
     if (r.count == 0) return PST_OK;  // nothing but non-finite points: no grid, `out` untouched
     grid = pmf_grid_over(r.min_x, r.min_y, r.max_x, r.max_y, cell_size, who);
   }
@@ -162,8 +123,7 @@ int pst_rasterize(const pst_buffer* b, const double* d_values, const uint8_t* d_
   } else {
     // the planes (host results only) | keys a | keys b | values a | the order = the buffer index of every sorted position | the values in
     // sorted order | the directory | the heavy cells | their number | their chunk partials | sort and scan scratch
-    unsigned cell_bits = 0;
-    while ((1ull << cell_bits) < cells) ++cell_bits;
+    const unsigned cell_bits = pstk::bits_for(cells);
     const uint32_t nonmember_key = 1u << cell_bits;  // at most 2^28
     size_t sort_bytes = 0, scan_bytes = 0;
     PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, cell_bits + 1, s, true));

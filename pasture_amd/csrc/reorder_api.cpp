@@ -6,40 +6,19 @@
 #include <memory>
 #include <utility>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
 namespace {
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_REORDER_TIMES=1: {bounds + keys, sort, gather} of every synchronous call
 
-// PST_REORDER_TIMES=1: stream events around the three phases {bounds + keys, sort, gather} of every synchronous call
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_REORDER_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
+bool times_wanted() {
+  static const bool wanted = env_nonzero("PST_REORDER_TIMES");
+  return wanted;
+}
 
 struct TempDev {
   uint8_t* p = nullptr;
@@ -142,7 +121,7 @@ void gather_checked(const pst_buffer& src, const void* indices, uint32_t index_b
   if (seen[1])
     throw Error(PST_ERR_RANGE, who + ": " + std::to_string(seen[1]) + " of the indices are out of range (the largest is " + std::to_string(seen[0]) + ", src has " +
                                    std::to_string(src.len) + " points)");
-  PhaseEvents events;  // (a gather has no key and no sort phase: those two read as zero)
+  PhaseEvents<3> events(times_wanted(), t_phase_ms);  // (a gather has no key and no sort phase: those two read as zero)
   for (int i = 0; i < 3; ++i) events.mark(i, s);
   launch_gather(src, idx_dev, index_bits, count, dst, dst_first, nullptr, s);
   events.mark(3, s);
@@ -156,7 +135,7 @@ void check_order_length(size_t n, const std::string& who) {
 
 // keys (by `fill`) -> stable sort with the element numbers as values -> d_order.  fill(keys32, keys64, vals) leaves vals alone for 32-bit keys.
 template <typename Fill>
-void sort_order(size_t n, bool keys64, unsigned end_bit, uint32_t* d_order, hipStream_t s, PhaseEvents& events, const std::string& who, Fill&& fill) {
+void sort_order(size_t n, bool keys64, unsigned end_bit, uint32_t* d_order, hipStream_t s, PhaseEvents<3>& events, const std::string& who, Fill&& fill) {
   size_t sort_bytes = 0;
   if (keys64) PST_HIP_CHECK(pstk::sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, s));
   else PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, end_bit, s, true));
@@ -252,8 +231,7 @@ int pst_sort_order_by_attribute_device(const pst_buffer* b, const char* name, co
   const DataType type = DataType::from_c(dt);
   if (!(type.is_scalar() || type.is_vec3())) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": only numeric attributes have a sort order (not " + type.display() + ")");
   if (component >= type.num_components()) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": component beyond the datatype");
-  const Member* m = b->layout.find(AttributeDef{name, type});
-  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& m = required(b->layout.find(AttributeDef{name, type}));
   const size_t n = b->len;
   if (n == 0) return PST_OK;
   ensure_device();
@@ -261,8 +239,8 @@ int pst_sort_order_by_attribute_device(const pst_buffer* b, const char* name, co
   hipStream_t s = current_stream();
   const uint32_t ct = type.comp_type();
   const uint32_t width = (uint32_t)(type.size() / type.num_components());  // bytes of a component
-  const AttrView v = attr_view(*b, m);
-  PhaseEvents events;
+  const AttrView v = attr_view(*b, &m);
+  PhaseEvents<3> events(times_wanted(), t_phase_ms);
   events.mark(0, s);
   sort_order(n, width == 8, 8 * width, d_order, s, events, who, [&](uint32_t* k32, unsigned long long* k64, uint32_t* vals) {
     return pstk::reorder_attribute_keys(v.addr + (uint64_t)component * width, v.stride, n, ct, descending != 0, k32, k64, vals, s);
@@ -279,25 +257,21 @@ int pst_morton_order_device(const pst_buffer* b, uint32_t dims, uint32_t bits, u
   const uint32_t max_bits = dims == 2 ? 31 : 21;
   if (bits > max_bits) throw Error(PST_ERR_INVALID_ARGUMENT, who + ": bits per axis must be 1 .. " + std::to_string(max_bits) + " (0: that maximum)");
   if (bits == 0) bits = max_bits;
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   const size_t n = b->len;
   if (n == 0) return PST_OK;
   ensure_device();
   check_order_length(n, who);
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
-  PhaseEvents events;
+  const pstk::Positions pos = positions_of(*b, pm);
+  PhaseEvents<3> events(times_wanted(), t_phase_ms);
   events.mark(0, s);
-  pstk::SampleBounds r{};
+  FiniteBounds r{};
   {
     ScratchLayout layout;
     const size_t off_partials = layout.add(pstk::sample_bounds_partials_bytes(n)), off_rec = layout.add(256);
     Scratch scratch(layout, s, who.c_str());
-    pstk::SampleBounds* rec = scratch.at<pstk::SampleBounds>(off_rec);
-    if (!pstk::sample_bounds(pos, scratch.at<void>(off_partials), rec, s)) throw hip_failure(who + ": bounds launch failed: ");
-    PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-    stream_sync(s);
+    r = finite_bounds_folded(pos, scratch.at<void>(off_partials), scratch.at<pstk::SampleBounds>(off_rec), s, who);
   }
   pstk::MortonGrid g{};
   g.dims = dims;
@@ -322,7 +296,7 @@ int pst_shuffle_order_device(uint64_t n, uint64_t seed, uint32_t* d_order) {
   ensure_device();
   check_order_length(n, who);
   hipStream_t s = current_stream();
-  PhaseEvents events;
+  PhaseEvents<3> events(times_wanted(), t_phase_ms);
   events.mark(0, s);
   sort_order(n, true, 64, d_order, s, events, who,
              [&](uint32_t*, unsigned long long* k64, uint32_t* vals) { return pstk::reorder_shuffle_keys(n, seed, k64, vals, s); });

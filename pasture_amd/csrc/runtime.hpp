@@ -109,6 +109,16 @@ inline const Member* position_vec3f64(const pst_buffer& b) {
   pos.datatype.kind = PST_VEC3F64;
   return b.layout.find(pos);
 }
+// what Layout::find returned, or the panic of view_attribute on a layout without the attribute
+inline const Member& required(const Member* m) {
+  if (!m) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  return *m;
+}
+inline const Member& position_member(const pst_buffer& b) { return required(position_vec3f64(b)); }
+// the kernels' point indices are uint32_t, and the largest sixteen values are kept free
+inline void check_point_count(size_t n, const std::string& who) {
+  if (n >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
+}
 
 // max_distance of the neighbour searches (nn_api.cpp, hag_api.cpp), checked; returns m2 = max_distance * max_distance, rounded once
 inline double checked_m2(double max_distance, const char* who) {
@@ -144,30 +154,6 @@ inline pstk::PmfGrid pmf_grid_over(double min_x, double min_y, double max_x, dou
   return g;
 }
 
-// The uniform grid over an AABB of finite points (clusters_api.cpp, sample_api.cpp).  The edge is the tolerance times (1 + 2^-20) -- STRICTLY
-// larger, by far more than any rounding of the cell numbers (the argument is at the head of clusters.hip) -- and is doubled until no axis
-// needs more than 2^21 - 1 cells: coarser cells cost pair tests, never exactness.  dim = cell of the largest coordinate + 1, by the expression
-// the key kernel evaluates per point.
-inline pstk::ClusterGrid cluster_grid_over(const double min[3], const double max[3], double tolerance, const std::string& who) {
-  constexpr uint32_t kMaxCellsPerAxis = (1u << 21) - 1;  // 21 key bits per axis: 63 in all, and one more bit tells the all-ones key apart
-  pstk::ClusterGrid g{};
-  double extent[3];
-  for (int a = 0; a < 3; ++a) {
-    g.min[a] = min[a];
-    extent[a] = max[a] - g.min[a];
-    if (!std::isfinite(extent[a])) throw Error(PST_ERR_UNSUPPORTED, who + ": the extent of the finite points overflows f64");
-  }
-  g.edge = tolerance * (1.0 + 0x1p-20);
-  while (extent[0] / g.edge >= (double)kMaxCellsPerAxis || extent[1] / g.edge >= (double)kMaxCellsPerAxis || extent[2] / g.edge >= (double)kMaxCellsPerAxis) g.edge *= 2.0;
-  for (int a = 0; a < 3; ++a) {
-    g.dim[a] = (uint32_t)(extent[a] / g.edge) + 1;
-    uint32_t bits = 0;  // key bits that hold the cell numbers 0 .. dim - 1
-    while ((1ull << bits) < g.dim[a]) ++bits;
-    g.bits[a] = bits;
-  }
-  return g;
-}
-
 // A call's block of device scratch, as a rule carved by a ScratchLayout: allocated on the stream, released in stream order by the destructor
 struct Scratch {
   pstk::DevBuf buf;
@@ -194,6 +180,11 @@ bool specialised_kernel_ready(bool src_aos, uint64_t src_base, uint32_t src_stri
 PlanEntry identity_entry(const Member& src, const Member& dst);
 
 void stream_sync(hipStream_t s);
+// every byte of a caller's result array, in device (stream-ordered) or in host memory
+inline void fill_result(void* p, int byte, size_t bytes, bool on_device, hipStream_t s) {
+  if (on_device) PST_HIP_CHECK(hipMemsetAsync(p, byte, bytes, s));
+  else std::memset(p, byte, bytes);
+}
 // OwningBuffer::resize; zero_fill = false leaves new points uninitialised (callers that overwrite every byte)
 void resize_buffer(pst_buffer& b, size_t count, bool zero_fill);
 

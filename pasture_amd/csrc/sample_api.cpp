@@ -1,10 +1,11 @@
-// pst_poisson_disk_mask / pst_sample_priorities / pst_sample_kernel_shape / pst_sample_phase_times: argument checks, the grid, the scratch
-// layout, the loop of decision rounds and the order of the launches of sample.hip (where the definitions and the ordering argument are).
+// pst_poisson_disk_mask / pst_sample_priorities / pst_sample_kernel_shape / pst_sample_phase_times: argument checks, the scratch layout, the
+// loop of decision rounds and the order of the launches of sample.hip (where the definitions and the ordering argument are; the grid is
+// cluster_grid.hpp's, the index build cluster_index.hpp's).
 #include <cmath>
 #include <cstring>
 
-#include "device_sort.hpp"
-#include "runtime.hpp"
+#include "cluster_index.hpp"
+#include "phase_events.hpp"
 
 using namespace pst;
 
@@ -12,33 +13,7 @@ namespace {
 
 enum : uint32_t { kShuffled = 0, kIndexOrder = 1 };  // PST_SAMPLE_SHUFFLED, PST_SAMPLE_INDEX_ORDER
 
-thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};
-
-// PST_SAMPLE_TIMES=1: stream events around the three phases of every call (tools/bench_sample.py reads them through pst_sample_phase_times)
-struct PhaseEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on;
-  PhaseEvents() {
-    static const bool wanted = env_nonzero("PST_SAMPLE_TIMES");
-    on = wanted;
-    if (on)
-      for (auto& ev : e) PST_HIP_CHECK(hipEventCreate(&ev));
-  }
-  ~PhaseEvents() {
-    for (auto ev : e)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void mark(int i, hipStream_t s) {
-    if (on) PST_HIP_CHECK(hipEventRecord(e[i], s));
-  }
-  void read() {  // after the stream has been synchronised
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      if (on) PST_HIP_CHECK(hipEventElapsedTime(&ms, e[i], e[i + 1]));
-      t_phase_ms[i] = ms;
-    }
-  }
-};
+thread_local double t_phase_ms[3] = {0.0, 0.0, 0.0};  // PST_SAMPLE_TIMES=1 (tools/bench_sample.py reads them through pst_sample_phase_times)
 
 }  // namespace
 
@@ -77,17 +52,16 @@ int pst_poisson_disk_mask(const pst_buffer* b, double radius, uint32_t order, ui
   const double r2 = radius * radius;
   if (!std::isfinite(radius) || !(radius > 0.0) || !std::isnormal(r2))
     throw Error(PST_ERR_INVALID_ARGUMENT, who + ": radius must be finite and positive, and its square a normal number");
-  const Member* pm = position_vec3f64(*b);
-  if (!pm) throw Error(PST_ERR_MISSING_ATTRIBUTE, "Attribute not found in PointLayout of buffer");
+  const Member& pm = position_member(*b);
   ensure_device();
-  if (b->len >= 0xFFFFFFF0ull) throw Error(PST_ERR_UNSUPPORTED, who + ": more than 2^32 - 17 points per call");
+  check_point_count(b->len, who);
   *kept = 0;
   if (rounds) *rounds = 0;
   const size_t n = b->len;
   if (n == 0) return PST_OK;  // no points: nothing kept, no mask byte to write
 
   hipStream_t s = current_stream();
-  const pstk::Positions pos = positions_of(*b, *pm);
+  const pstk::Positions pos = positions_of(*b, pm);
   const bool mask_on_device = mask_memkind == PST_MEM_DEVICE;
 
   // One block of scratch.  The sort's input pair is dead once the sort has run; the rounds' bookkeeping lives in it:
@@ -101,20 +75,14 @@ int pst_poisson_disk_mask(const pst_buffer* b, double radius, uint32_t order, ui
   PST_HIP_CHECK(pstk::sort_pairs_u64(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, 64, s));
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, n + 1, s));
   const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-  const size_t b4 = up256((n + 1) * 4), b8 = 2 * b4;
   ScratchLayout layout;
-  const size_t off_keys_a = layout.add(b8), off_keys_b = layout.add(b8), off_vals_a = layout.add(b4), off_order = layout.add(b4);
-  const size_t off_xs = layout.add(b8), off_ys = layout.add(b8), off_zs = layout.add(b8), off_state = layout.add(n), off_flags = layout.add(b4);
-  const size_t off_active = layout.add(b4), off_partials = layout.add(pstk::sample_bounds_partials_bytes(n)), off_rec = layout.add(256), off_kept = layout.add(256);
+  ClusterIndex ix;
+  ix.carve(layout, n);
+  const size_t off_state = layout.add(n), off_flags = layout.add(ix.b4);
+  const size_t off_active = layout.add(ix.b4), off_partials = layout.add(pstk::sample_bounds_partials_bytes(n)), off_rec = layout.add(256), off_kept = layout.add(256);
   const size_t off_tmp = layout.add(tmp_bytes), off_mask = layout.add(mask_on_device ? 0 : n);
   Scratch scratch(layout, s, who.c_str());
-  uint64_t* keys_a = scratch.at<uint64_t>(off_keys_a);
-  uint64_t* keys_b = scratch.at<uint64_t>(off_keys_b);
-  uint32_t* vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t* order_of = scratch.at<uint32_t>(off_order);
-  double* xs = scratch.at<double>(off_xs);
-  double* ys = scratch.at<double>(off_ys);
-  double* zs = scratch.at<double>(off_zs);
+  ix.bind(scratch);
   uint8_t* state = scratch.at<uint8_t>(off_state);
   uint32_t* flags = scratch.at<uint32_t>(off_flags);
   pstk::SampleBounds* rec = scratch.at<pstk::SampleBounds>(off_rec);
@@ -122,40 +90,33 @@ int pst_poisson_disk_mask(const pst_buffer* b, double radius, uint32_t order, ui
   void* tmp = scratch.at<void>(off_tmp);
   uint8_t* mask_dev = mask_on_device ? mask : scratch.at<uint8_t>(off_mask);
 
-  PhaseEvents events;
+  static const bool timed = env_nonzero("PST_SAMPLE_TIMES");
+  PhaseEvents<3> events(timed, t_phase_ms);
   events.mark(0, s);
   // ---- index build: AABB of the finite points -> (host: grid) -> keys -> sort -> gather
-  if (!pstk::sample_bounds(pos, scratch.at<void>(off_partials), rec, s)) throw hip_failure(who + ": bounds launch failed: ");
-  pstk::SampleBounds r{};
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  const uint32_t nf = (uint32_t)r.count;
+  const FiniteBounds bounds = finite_bounds_folded(pos, scratch.at<void>(off_partials), rec, s, who);
+  const uint32_t nf = (uint32_t)bounds.count;
   if (nf == 0) {  // nothing but non-finite points: nothing kept, no round
-    if (mask_on_device) PST_HIP_CHECK(hipMemsetAsync(mask, 0, n, s));
-    else std::memset(mask, 0, n);
+    fill_result(mask, 0, n, mask_on_device, s);
     stream_sync(s);
     return PST_OK;
   }
-  const pstk::ClusterGrid grid = cluster_grid_over(r.min, r.max, radius, who);
-  const unsigned key_bits = grid.bits[0] + grid.bits[1] + grid.bits[2];
-  if (!pstk::cluster_keys(pos, grid, (unsigned long long*)keys_a, vals_a, s)) throw hip_failure(who + ": key launch failed: ");
-  size_t bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::sort_pairs_u64(tmp, bytes, keys_a, keys_b, vals_a, order_of, n, key_bits + 1, s));
-  if (!pstk::nn_gather(pos, order_of, nf, xs, ys, zs, s)) throw hip_failure(who + ": gather launch failed: ");
+  const pstk::ClusterGrid grid = cluster_grid_over(bounds, radius, who);
+  ix.build(pos, grid, nf, tmp, tmp_bytes, s, who, true);
   PST_HIP_CHECK(hipMemsetAsync(state, 0, nf, s));  // every point undecided
   PST_HIP_CHECK(hipMemsetAsync(kept_dev, 0, sizeof(*kept_dev), s));
   events.mark(1, s);
   // ---- decision rounds: decide the active points, compact the still undecided ones into the next active list, read back their number.  The
   // undecided point of smallest key decides in every launch, so m falls to 0; there is no cap.
-  unsigned long long* offsets = (unsigned long long*)keys_a;
-  uint32_t* lists[2] = {vals_a, scratch.at<uint32_t>(off_active)};
+  unsigned long long* offsets = (unsigned long long*)ix.keys_a;
+  uint32_t* lists[2] = {ix.vals_a, scratch.at<uint32_t>(off_active)};
   const uint32_t* active = nullptr;  // the first round: every sorted point
   uint32_t m = nf, launches = 0;
   while (m) {
-    if (!pstk::sample_decide((const unsigned long long*)keys_b, xs, ys, zs, order_of, nf, grid, r2, order == kShuffled, seed, active, m, state, flags, s))
+    if (!pstk::sample_decide(ix.sorted_keys(), ix.xs, ix.ys, ix.zs, ix.order, nf, grid, r2, order == kShuffled, seed, active, m, state, flags, s))
       throw hip_failure(who + ": decision launch failed: ");
     ++launches;
-    bytes = tmp_bytes;
+    size_t bytes = tmp_bytes;
     PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, (size_t)m + 1, s));
     uint32_t* next = lists[launches & 1];
     if (!pstk::sample_compact(active, flags, offsets, m, next, s)) throw hip_failure(who + ": compaction launch failed: ");
@@ -168,7 +129,7 @@ int pst_poisson_disk_mask(const pst_buffer* b, double radius, uint32_t order, ui
   }
   events.mark(2, s);
   // ---- the mask and the kept count
-  if (!pstk::sample_mask(order_of, state, n, nf, mask_dev, kept_dev, s)) throw hip_failure(who + ": mask launch failed: ");
+  if (!pstk::sample_mask(ix.order, state, n, nf, mask_dev, kept_dev, s)) throw hip_failure(who + ": mask launch failed: ");
   events.mark(3, s);
   unsigned long long kept_host = 0;
   PST_HIP_CHECK(hipMemcpyAsync(&kept_host, kept_dev, sizeof(kept_host), hipMemcpyDeviceToHost, s));
