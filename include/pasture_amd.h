@@ -549,6 +549,75 @@ int pst_dbscan_kernel_shape(uint32_t* points_per_block);
  * switch.  Host only. */
 int pst_dbscan_phase_times(double ms[4]);
 
+/* ---- Region growing (smooth surface patches) ------------------------------------------------------------------------------------------------
+ * What PCL's RegionGrowing, CloudCompare's facet extraction and PDAL pipelines built on filters.normal compute (the reference has none of
+ * them): the cloud is split into its smooth surface patches -- roof faces, walls, the road, the sides of a box -- by joining neighbouring
+ * points whose normals agree.  Where pst_euclidean_clusters and pst_dbscan group by distance alone, so that a building comes back as one
+ * blob, this call separates what meets at an edge.  Every floating-point operation below is a separately rounded f64 operation;
+ * tests/region_ref.py restates the definition in numpy.
+ *   inputs:        n points; k in 1 .. 64; neighbour lists knn uint32 [n][k], which need not be sorted; normals f64 [n][3]; curvature
+ *                  f64 [n], nullable; min_abs_cos in [0, 1]; curvature_threshold; max_distance (+inf: no limit); min_size >= 1 and
+ *                  max_size >= min_size.
+ *   valid point:   all three components of its normal are finite.  Any other point gets the label 0xFFFFFFFF and is nobody's neighbour.
+ *   smooth point:  a valid point with curvature[i] <= curvature_threshold; a NaN curvature compares false.  Without a curvature array every
+ *                  valid point is smooth.  Smooth points carry the regions, as core points carry the clusters of pst_dbscan.
+ *   slot:          slot t of point i names j = knn[i][t] and COUNTS iff j < n (the 0xFFFFFFFF padding and any out-of-range index are
+ *                  skipped and never dereferenced), j != i, j is valid, and max_distance == +inf or d <= max_distance with
+ *                  d = sqrt((dx*dx + dy*dy) + dz*dz), dx = p_j.x - p_i.x (y, z alike): the slot distance of pst_knn_search_device.  A NaN d
+ *                  compares false.  Positions are read only when max_distance is finite.
+ *   agreement:     i and j agree iff fabs((ni.x*nj.x + ni.y*nj.y) + ni.z*nj.z) >= min_abs_cos.  The normals are taken as given: they are
+ *                  neither normalised nor oriented, and the absolute value makes their orientation irrelevant, as in PCL.
+ *   region:        a connected component of the undirected graph on the SMOOTH points in which {i, j} is an edge iff both are smooth, they
+ *                  agree, and j is in a counting slot of i OR i is in a counting slot of j.  kNN lists are not symmetric; one direction is
+ *                  enough for an edge.
+ *   rim:           a valid point that is not smooth.  It joins the region of the first slot, in slot order, that counts, names a smooth
+ *                  point and agrees with it; without such a slot it is in no region.  Nothing is united through a rim point.
+ *   size filter:   the clusters' rule: sizes are smooth plus rim members; regions of fewer than min_size or more than max_size points are
+ *                  dropped, their points are in no region.
+ *   numbering:     the kept regions are numbered 0, 1, ... by descending size, ties by ascending smallest member index (index in the buffer).
+ *   labels:        labels[i] = the region number of point i, or 0xFFFFFFFF when it is in none.
+ * The result depends on nothing else: not on the schedule, the storage or the launch shape.  Two calls write the same bytes (sizes are integer
+ * sums, the rim choice is the first slot in slot order, the numbering is a stable sort).
+ * How this differs from PCL's RegionGrowing: PCL grows sequentially from the seed of lowest curvature; it reaches j only through lists that
+ * contain j, and it gives a point to the first region that arrives at it, which depends on the order of the visit.  PCL may also start a
+ * region from a point above the curvature threshold when no other seed is left.  This definition is the order-free closure of PCL's rule:
+ * the edges between smooth points are the same (taken in either direction), so the partition of the smooth points is PCL's wherever PCL's
+ * does not depend on its visiting order; only the rim points (PCL: whichever region reaches them first; here: the first agreeing slot) and
+ * the seedless regions (PCL: may start from a point above the threshold; here: never) differ.  PCL's residual test is not part of it.
+ * Null b, d_knn, d_normals, labels or counts, an invalid memkind, k outside 1 .. 64, min_abs_cos outside [0, 1] or NaN, a NaN
+ * curvature_threshold, a NaN or negative max_distance, min_size == 0, max_size < min_size -> PST_ERR_INVALID_ARGUMENT; Position3D not stored
+ * as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE (interleaved or columnar, owned, sliced or external, at any byte offset; the attribute is
+ * required even when max_distance is +inf); all of these are answered before a device is looked for.  An empty buffer is PST_OK with zero
+ * counts, answered on the host; without a device the call is PST_ERR_NO_DEVICE, never a CPU path; 2^32 - 16 points and more ->
+ * PST_ERR_UNSUPPORTED.  A cloud without a valid normal gets all-0xFFFFFFFF labels, zero mask bytes and zero counts.
+ * Cost: one coalesced pass over the n * k list elements with one 24-byte gather per slot whose both ends are smooth, the union-find over the
+ * agreeing slots, one walk of its own list for every rim point, and the clusters' numbering. */
+/* Synchronous: the host reads the number of regions before the numbering sort, as pst_dbscan does.  d_knn, d_normals, d_curvature: DEVICE
+ * memory.  labels: len x uint32, required; smooth: len bytes, nullable, 1 = smooth point, 0 otherwise.  Both in device memory (memkind =
+ * PST_MEM_DEVICE) or both in host memory (anything else), the convention of pst_dbscan.  sizes (host, nullable): sizes[c] = points of region
+ * c, when the kept regions fit sizes_capacity; more kept regions than that -> PST_ERR_RANGE with the counts set and the labels written.
+ * counts = {kept regions, smooth points, labelled points}.  pst_cluster_mask_device turns the labels into a filter mask. */
+int pst_region_growing_from_knn(const pst_buffer* b, size_t k, const uint32_t* d_knn, const double* d_normals, const double* d_curvature,
+                                double min_abs_cos, double curvature_threshold, double max_distance, uint64_t min_size, uint64_t max_size,
+                                uint32_t* labels, uint8_t* smooth, uint32_t memkind, uint64_t* sizes, size_t sizes_capacity, uint64_t counts[3]);
+/* The search of pst_geometric_features (the same lists, checks and limits: k = 3 .. 64, at least 3 points, fewer than 2^32 - 16, Vec3f64),
+ * then its kernel for e3 (the normals) and PST_FEATURE_SURFACE_VARIATION = l3 / S (the curvature, PCL's) with the same max_distance, then
+ * the steps of the call above on what they wrote.  A point with fewer than 3 valid neighbours has a NaN normal and is in no region.
+ * d_normals f64 [n][3], d_curvature f64 [n], d_knn uint32 [n][k] (device, each nullable): also receive what the regions were grown from;
+ * scratch otherwise.  The parameters are checked before a device is looked for, then the device, then the length: an empty buffer is PST_OK
+ * with zero counts; one of 1 or 2 points is PST_ERR_TOO_FEW_POINTS. */
+int pst_region_growing(const pst_buffer* b, size_t k, double min_abs_cos, double curvature_threshold, double max_distance, uint64_t min_size,
+                       uint64_t max_size, uint32_t* labels, uint8_t* smooth, uint32_t memkind, uint64_t* sizes, size_t sizes_capacity,
+                       uint64_t counts[3], double* d_normals, double* d_curvature, uint32_t* d_knn);
+/* The link kernel's seams for this k (tests place their sizes around them; each pointer optional): points whose whole neighbour lists one
+ * workgroup owns, and its threads (it walks the lists that many elements at a time).  k outside 1 .. 64 -> PST_ERR_INVALID_ARGUMENT.  Host
+ * only. */
+int pst_region_kernel_shape(size_t k, uint32_t* points_per_block, uint32_t* threads);
+/* Measurement aid.  With PST_REGION_TIMES=1 in the environment both calls bracket their three phases with stream events; this returns the
+ * calling thread's last call: ms = {search + features (zero from lists), classify + link, attach + numbering}.  Zeros without the switch.
+ * Host only. */
+int pst_region_phase_times(double ms[3]);
+
 /* ---- Minimum-distance (Poisson-disk) subsampling ----------------------------------------------------------------------------------------
  * What PDAL's filters.sample, CloudCompare's "subsample by space" and lidR's decimate_points compute (the reference has none of them): a
  * subset of the ORIGINAL points in which no two are closer than a radius, as a byte mask that pst_buffer_filter / pst_buffer_filter_into

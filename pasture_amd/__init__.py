@@ -14,7 +14,8 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          ransac_line_fit, ransac_plane, ransac_plane_fit, ransac_sample_indices, OutlierStatistics, knn_search, knn_search_device,
                          outlier_kernel_shape, radius_outlier_mask, remove_radius_outliers, remove_statistical_outliers, statistical_outlier_mask,
                          NO_CLUSTER, cluster_kernel_shape, cluster_mask, euclidean_clusters, extract_clusters, DbscanResult, dbscan,
-                         dbscan_kernel_shape, dbscan_phase_times, extract_dbscan_clusters, NO_MATCH, NearestNeighbourIndex,
+                         dbscan_kernel_shape, dbscan_phase_times, extract_dbscan_clusters, RegionGrowingResult, extract_regions, region_growing,
+                         region_growing_from_knn, region_kernel_shape, region_phase_times, NO_MATCH, NearestNeighbourIndex,
                          cloud_to_cloud_distances, distance_mask, icp, icp_plane, icp_plane_step, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape,
                          PmfParameters, classify_ground, extract_ground, grid_dilate, grid_erode, ground_mask, pmf_grid, pmf_kernel_shape, pmf_phase_times,
                          pmf_schedule, remove_ground, classification_mask, hag_kernel_shape, hag_phase_times, height_above_ground,

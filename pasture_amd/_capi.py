@@ -238,6 +238,10 @@ _PRODUCT_SIGNATURES = {
     "dbscan": [_P, C.c_double, C.c_uint64, _P, _P, C.c_uint32, _U64P, _SZ, _U64P],
     "dbscan_kernel_shape": [_U32P],
     "dbscan_phase_times": [_D3],
+    "region_growing_from_knn": [_P, _SZ, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32, _U64P, _SZ, _U64P],
+    "region_growing": [_P, _SZ, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32, _U64P, _SZ, _U64P, _P, _P, _P],
+    "region_kernel_shape": [_SZ, _U32P, _U32P],
+    "region_phase_times": [_D3],
     "buffer_gather": [_P, _P, C.c_uint32, C.c_uint32, _SZ, _P, _SZ],
     "buffer_gather_async": [_P, _P, C.c_uint32, _SZ, _P, _SZ, _P],
     "buffer_take": [_P, _P, C.c_uint32, C.c_uint32, _SZ, C.c_uint32, _PP],

@@ -562,6 +562,153 @@ def dbscan_phase_times(api=None):
     return _phase_times(api, "dbscan_phase_times", 4)
 
 
+# ---- region growing: smooth surface patches (include/pasture_amd.h) --------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class RegionGrowingResult:
+    labels: Optional[np.ndarray]  # uint32, NO_CLUSTER for points in no kept region; None when they went to device memory
+    smooth: Optional[np.ndarray]  # bool, True for smooth points; None when it went to device memory or was not asked for
+    sizes: np.ndarray             # uint64, sizes[c] = smooth + rim points of region c
+    n_smooth: int
+    n_labelled: int
+    normals: Optional[np.ndarray] = None    # (n, 3) float64, region_growing(return_inputs=True): what the regions were grown from
+    curvature: Optional[np.ndarray] = None  # (n,) float64
+    knn: Optional[np.ndarray] = None        # (n, k) uint32, 0xFFFFFFFF padding
+
+_REGION_SIZES_FIRST = 1 << 16  # sizes asked for by the first call; more regions than that cost a second one
+
+
+def _region_call(buffer: _Buffer, call, device_labels_ptr, device_smooth_ptr, want_smooth: bool):
+    """call(labels, smooth, memkind, sizes, capacity, counts) runs one of the two entries; (labels, smooth, sizes, counts) with the sizes complete"""
+    n = buffer.len()
+    on_device = device_labels_ptr is not None
+    if device_smooth_ptr is not None and not on_device:
+        raise ValueError("device_smooth_ptr needs device_labels_ptr: labels and smooth mask share one memory kind")
+    labels = None if on_device else np.full(n, NO_CLUSTER, dtype=np.uint32)
+    smooth = None if on_device or not want_smooth else np.zeros(n, dtype=np.uint8)
+    if on_device:
+        lptr, sptr = C.c_void_p(int(device_labels_ptr) or None), C.c_void_p(int(device_smooth_ptr) if device_smooth_ptr else None)
+    else:
+        lptr, sptr = C.c_void_p(labels.ctypes.data if n else 1), C.c_void_p((smooth.ctypes.data if n else 1) if smooth is not None else None)
+    kind = 0 if on_device else 1
+    counts = (C.c_uint64 * 3)()
+    sizes = np.zeros(min(n, _REGION_SIZES_FIRST), dtype=np.uint64)
+    from ._capi import ERR_RANGE, PastureError
+    try:
+        call(lptr, sptr, kind, _u64(sizes), len(sizes), counts)
+    except PastureError as e:
+        if e.code != ERR_RANGE:
+            raise
+        sizes = np.zeros(counts[0], dtype=np.uint64)  # (the counts are set and the labels written: only the sizes are missing)
+        call(lptr, sptr, kind, _u64(sizes), len(sizes), counts)
+    return labels, None if smooth is None else smooth.astype(bool), sizes[:counts[0]].copy(), counts
+
+
+def _device_input(api, values, datatype, dtype, count: int, what: str):
+    """(address, keep-alive) of `count` values: a caller's device address as it is, a numpy array copied into a device array of the library's"""
+    if values is None:
+        return 0, None
+    if isinstance(values, (int, np.integer)):
+        return int(values), None
+    a = np.ascontiguousarray(values)
+    if a.size != count:
+        raise ValueError(f"{what} must hold {count} values")
+    if dtype == np.uint32:
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{what} must be an integer array")
+        a = (a.astype(np.int64).reshape(-1) & 0xFFFFFFFF).astype(np.uint32)  # (-1: no neighbour)
+    else:
+        a = a.astype(dtype).reshape(-1)
+    dev = _DeviceArray(api, datatype, count)
+    if count:
+        dev.buffer.set_attribute_range(dev.attribute, range(0, count), a)
+    return dev.ptr or 1, dev
+
+
+def region_growing_from_knn(buffer: _Buffer, k: int, knn, normals, curvature=None, min_abs_cos: float = 1.0, curvature_threshold: float = float("inf"),
+                            max_distance: float = float("inf"), min_size: int = 1, max_size: int = _MAX_SIZE, device_labels_ptr: Optional[int] = None,
+                            device_smooth_ptr: Optional[int] = None, return_smooth: bool = True) -> RegionGrowingResult:
+    """Smooth surface patches over given neighbour lists: knn (n, k) integers (-1 or anything >= n: no neighbour), normals (n, 3) and an
+    optional curvature (n,), each a numpy array or the address of such an array in DEVICE memory (uint32 / float64).  A point is smooth when
+    its normal is finite and its curvature <= curvature_threshold; smooth points whose normals agree, |ni . nj| >= min_abs_cos, and of which
+    one lists the other (within max_distance) are in one region; a point that is not smooth joins the region of its first agreeing smooth
+    neighbour and bridges nothing.  Regions of min_size .. max_size points are kept and numbered by descending size (ties: ascending smallest
+    member index).  With device_labels_ptr the labels and, at device_smooth_ptr (optional), the smooth bytes go to DEVICE memory."""
+    from .layout import PointAttributeDataType as T
+    n = buffer.len()
+    k = int(k)
+    count = n * k if 1 <= k <= 64 else 0
+    kp, keep_k = _device_input(buffer.api, knn, T.U32, np.uint32, count, "knn")
+    np_, keep_n = _device_input(buffer.api, normals, T.F64, np.float64, n * 3, "normals")
+    cp, keep_c = _device_input(buffer.api, curvature, T.F64, np.float64, n, "curvature")
+
+    def call(lptr, sptr, kind, sizes, capacity, counts):
+        buffer.api.region_growing_from_knn(buffer._h, k, C.c_void_p(kp or None), C.c_void_p(np_ or None), C.c_void_p(cp or None), min_abs_cos, curvature_threshold,
+                                           max_distance, min_size, max_size, lptr, sptr, kind, sizes, capacity, counts)
+    labels, smooth, sizes, counts = _region_call(buffer, call, device_labels_ptr, device_smooth_ptr, return_smooth)
+    del keep_k, keep_n, keep_c
+    return RegionGrowingResult(labels, smooth, sizes, int(counts[1]), int(counts[2]))
+
+
+def region_growing(buffer: _Buffer, k: int, smoothness_deg: float = 10.0, curvature_threshold: float = 0.02, max_distance: float = float("inf"), min_size: int = 1,
+                   max_size: int = _MAX_SIZE, min_abs_cos: Optional[float] = None, device_labels_ptr: Optional[int] = None, device_smooth_ptr: Optional[int] = None,
+                   return_smooth: bool = True, return_inputs: bool = False, normals_ptr: int = 0, curvature_ptr: int = 0, knn_ptr: int = 0) -> RegionGrowingResult:
+    """PCL's RegionGrowing on the device, in its order-free form: the library searches the k nearest neighbours (k = 3 .. 64), takes the normal
+    and the curvature (surface variation l3 / (l1 + l2 + l3)) of every point from their covariance, and grows regions as
+    region_growing_from_knn does.  Normals agree when the angle between them is at most smoothness_deg degrees (either orientation); the C
+    ABI takes min_abs_cos = cos of that angle, which can be given directly instead.  return_inputs: the result also carries the normals,
+    curvature and lists the regions were grown from; normals_ptr / curvature_ptr / knn_ptr: DEVICE memory that receives them."""
+    import math
+    from .layout import PointAttributeDataType as T
+    n = buffer.len()
+    k = int(k)
+    if min_abs_cos is None:
+        min_abs_cos = math.cos(math.radians(smoothness_deg))
+    kept = {}
+    if return_inputs:
+        ok = 3 <= k <= 64 and n >= 3  # (anything else is answered by the call's own checks)
+        kept = {"normals": _DeviceArray(buffer.api, T.F64, n * 3 if ok else 0), "curvature": _DeviceArray(buffer.api, T.F64, n if ok else 0),
+                "knn": _DeviceArray(buffer.api, T.U32, n * k if ok else 0)}
+        normals_ptr, curvature_ptr, knn_ptr = kept["normals"].ptr or 0, kept["curvature"].ptr or 0, kept["knn"].ptr or 0
+
+    def call(lptr, sptr, kind, sizes, capacity, counts):
+        buffer.api.region_growing(buffer._h, k, min_abs_cos, curvature_threshold, max_distance, min_size, max_size, lptr, sptr, kind, sizes, capacity, counts,
+                                  C.c_void_p(int(normals_ptr) or None), C.c_void_p(int(curvature_ptr) or None), C.c_void_p(int(knn_ptr) or None))
+    labels, smooth, sizes, counts = _region_call(buffer, call, device_labels_ptr, device_smooth_ptr, return_smooth)
+    extra = {}
+    if return_inputs:
+        extra = {"normals": kept["normals"].to_numpy().reshape(-1, 3), "curvature": kept["curvature"].to_numpy(), "knn": kept["knn"].to_numpy().reshape(-1, max(k, 1))}
+    return RegionGrowingResult(labels, smooth, sizes, int(counts[1]), int(counts[2]), **extra)
+
+
+def extract_regions(buffer: _Buffer, k: int, first_region: int = 0, region_count: int = 1, out_buffer_type=None, **parameters):
+    """(the points of regions first_region .. first_region + region_count - 1 in buffer order with all their attributes, sizes of ALL kept
+    regions): labels and mask stay in device memory.  region_count = 0xFFFFFFFF from region 0 drops the unlabelled points and keeps the rest.
+    parameters: those of region_growing.  `buffer` is columnar (filter is defined on HashMapBuffer)."""
+    from .layout import PointAttributeDataType as T
+    labels = _DeviceArray(buffer.api, T.U32, buffer.len())
+
+    def fill(mask_ptr):
+        sizes = region_growing(buffer, k, device_labels_ptr=labels.ptr or 1, **parameters).sizes
+        cluster_mask(labels.ptr, buffer.len(), first_region, region_count, mask_ptr, api=buffer.api)
+        return sizes
+    return _filter_by_device_mask(buffer, out_buffer_type, fill)
+
+
+def region_kernel_shape(k: int, api=None) -> dict:
+    """The seams of the link kernel at this k: points whose whole neighbour lists one workgroup owns, and its threads."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).region_kernel_shape(k, *[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "threads"), (x.value for x in v)))
+
+
+def region_phase_times(api=None):
+    """(search + features, classify + link, attach + numbering) in milliseconds of this thread's last region growing call; zeros unless
+    PST_REGION_TIMES=1 was set when the library first ran one."""
+    return _phase_times(api, "region_phase_times", 3)
+
+
 # ---- ground classification: the progressive morphological filter (include/pasture_amd.h) -------------------------------------------------------
 
 @dataclass(frozen=True)

@@ -421,6 +421,30 @@ bool dbscan_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min
 bool dbscan_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t clusters, const uint32_t* order, const uint32_t* root, const uint8_t* core, uint64_t n,
                    uint32_t nf, uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, uint8_t* core_out, hipStream_t stream);
 
+// Region growing over neighbour lists (region.hip; the checks, the scratch and the order of the launches are in region_api.cpp).  The seams
+// (pst_region_kernel_shape):
+constexpr uint32_t kRegionThreads = 256;            // threads of one workgroup of the link kernel; classify and attach: one lane per point
+uint32_t region_points_per_block(uint32_t k);       // points whose whole lists one workgroup of the link kernel owns: 256, 128, 64 or 32
+// state[i] = 0 (a normal component is not finite), 1 (rim) or 2 (smooth: valid and curvature[i] <= curvature_threshold; curvature nullable:
+// every valid point); parent[i] = i; *n_smooth (zeroed) += the smooth points, one integer atomic per wave
+bool region_classify(const double* normals, const double* curvature, double curvature_threshold, uint32_t n, uint8_t* state, uint32_t* parent, unsigned long long* n_smooth,
+                     hipStream_t stream);
+// unite(i, j) for every counting slot j of a smooth i that names a smooth point whose normal agrees; knn: uint32 [n][k], 1 <= k <= 64
+bool region_link(const Positions& pos, uint32_t k, const uint32_t* knn, const double* normals, const uint8_t* state, double min_abs_cos, double max_distance,
+                 uint32_t* parent, hipStream_t stream);
+// behind region_link: root[i] = the root of a smooth point / of the first agreeing smooth slot of a rim point / 0xFFFFFFFF; points per root
+// and the smallest index per root (both set up here)
+bool region_attach(const Positions& pos, uint32_t k, const uint32_t* knn, const double* normals, const uint8_t* state, double min_abs_cos, double max_distance,
+                   uint32_t* parent, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream);
+// flags[i] = 1 and root_at[i] = root where i is the smallest member of a region of min_size .. max_size points (flags: n + 1 elements, the
+// last one 0); *n_labelled (zeroed) += the kept sizes.  cluster_list_kept takes it from there.
+bool region_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint32_t n, uint64_t min_size, uint64_t max_size, uint32_t* flags, uint32_t* root_at,
+                 unsigned long long* n_labelled, hipStream_t stream);
+// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[i] = rank of root[i], 0xFFFFFFFF without a kept one;
+// smooth_out[i] = 1 iff state[i] == 2 (smooth_out nullable)
+bool region_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* root, const uint8_t* state, uint32_t n, uint32_t* rank_of_root,
+                   unsigned long long* sizes, uint32_t* labels, uint8_t* smooth_out, hipStream_t stream);
+
 // Gather by index and the keys of the device sort orders (reorder.hip; the checks, the scratch and the order of the launches are in
 // reorder_api.cpp).  The seams (pst_reorder_kernel_shape):
 constexpr uint32_t kReorderPointsPerBlock = 256;      // consecutive OUTPUT points one workgroup owns: one index per lane, read once
