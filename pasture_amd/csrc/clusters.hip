@@ -11,9 +11,10 @@
 //             Lower ids have lower or equal keys, so only five of the nine (y, z) rows can hold any: the four rows that sort before the point's
 //             own -- each one contiguous key range [x - 1, x + 1], found by two binary searches of the sorted keys -- and the own row up to the
 //             point itself.  Lanes of a wave are neighbours in the sorted order: they search the same ranges and read the same candidates.
-//   flatten   root per point, points per root (integer atomicAdd), smallest buffer index per root (atomicMin)
+//   flatten   root per point, points per root and smallest buffer index per root: the wave-folded tally of grid_index_device.hpp
 //   number    size filter, flag the smallest member of every kept component, exclusive scan (= the kept roots in ascending smallest-member
-//             order), one stable sort on 0xFFFFFFFF - size (ties keep that order), ranks back to the roots, labels to the points.
+//             order), one stable sort on 0xFFFFFFFF - size (ties keep that order), ranks back to the roots, labels to the points.  The flag,
+//             list and rank kernels below serve DBSCAN and the regions as well; cluster_numbering.hpp holds the host sequence for all three.
 //
 // The grid's cell edge is STRICTLY larger than the tolerance, by the relative margin 2^-20 (cluster_grid.hpp makes it, and doubles it until no
 // axis has more than 2^21 - 1 cells).  Why that is enough for "adjacent points are at most one cell apart on every axis": adjacency gives
@@ -38,7 +39,7 @@ namespace {
 
 constexpr uint32_t kP = pstk::kClusterPointsPerBlock;
 constexpr uint32_t kBoundsPoints = 1024;  // points per workgroup of the bounds fold, four per lane
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNone = kNoRoot;
 static_assert(kP == kBlock, "one lane per point");
 
 using Record = pstk::ClusterRecord;
@@ -107,28 +108,22 @@ __global__ __launch_bounds__(kBlock) void cluster_gather_kernel(Pos pos, const u
   parent[s] = s;
 }
 
-// ---- the traversal (the union-find and the binary search of the keys: grid_index_device.hpp) ----------------------------------------------------
+// ---- the traversal (the union-find, the binary search, the stencil rows and the predicate: grid_index_device.hpp) -------------------------------
 __global__ __launch_bounds__(kBlock) void cluster_traverse_kernel(const unsigned long long* __restrict__ keys, const double* __restrict__ xs, const double* __restrict__ ys,
                                                                   const double* __restrict__ zs, uint32_t nf, Grid g, double t2, uint32_t* parent) {
   const uint32_t s = blockIdx.x * kP + threadIdx.x;
   if (s >= nf) return;
-  const unsigned long long key = keys[s];
-  const uint32_t bx = g.bits[0], by = g.bits[1];
-  const uint32_t cx = (uint32_t)(key & ((1ull << bx) - 1)), cy = (uint32_t)((key >> bx) & ((1ull << by) - 1)), cz = (uint32_t)(key >> (bx + by));
-  const uint32_t x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.dim[0] ? cx + 1 : cx;
+  const Cell cell = cell_of_key(keys[s], g);
   const double px = xs[s], py = ys[s], pz = zs[s];
   // rows in key order below the own one: (z - 1, y - 1), (z - 1, y), (z - 1, y + 1), (z, y - 1); then the own row, which ends at s
 #pragma unroll 1
   for (int r = 0; r < 5; ++r) {
-    const int dz = r < 3 ? -1 : 0, dy = r < 3 ? r - 1 : r - 4;
-    if ((dz < 0 && cz == 0) || (dy < 0 && cy == 0) || (dy > 0 && cy + 1 >= g.dim[1])) continue;
-    const unsigned long long row = ((unsigned long long)(cz + dz) << (bx + by)) | ((unsigned long long)(cy + dy) << bx);
-    const uint32_t first = lower_bound(keys, s, row | x0);
-    const uint32_t last = r == 4 ? s : lower_bound(keys, s, (row | x1) + 1);  // (keys below s only: every candidate has a lower id)
-    for (uint32_t c = first; c < last; ++c) {
-      const double dx = xs[c] - px, dy2 = ys[c] - py, dz2 = zs[c] - pz;
-      if ((dx * dx + dy2 * dy2) + dz2 * dz2 <= t2) unite(parent, s, c);
-    }
+    unsigned long long row;
+    if (!stencil_row(cell, g, r < 3 ? -1 : 0, r < 3 ? r - 1 : r - 4, row)) continue;
+    const uint32_t first = lower_bound(keys, s, row | cell.x0);
+    const uint32_t last = r == 4 ? s : lower_bound(keys, s, (row | cell.x1) + 1);  // (keys below s only: every candidate has a lower id)
+    for (uint32_t c = first; c < last; ++c)
+      if (squared_distance(xs[c], ys[c], zs[c], px, py, pz) <= t2) unite(parent, s, c);
   }
 }
 
@@ -136,24 +131,24 @@ __global__ __launch_bounds__(kBlock) void cluster_traverse_kernel(const unsigned
 __global__ __launch_bounds__(kBlock) void cluster_flatten_kernel(uint32_t* parent, const uint32_t* __restrict__ order, uint32_t nf, uint32_t* __restrict__ root,
                                                                  uint32_t* size, uint32_t* min_index) {
   const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= nf) return;
-  const uint32_t r = find_root(parent, s);  // no union runs any more: what a lane finds IS the root
-  root[s] = r;
-  atomicAdd(size + r, 1u);
-  atomicMin(min_index + r, order[s]);
+  const bool live = s < nf;  // (no lane leaves before the wave-wide tally)
+  const uint32_t r = live ? find_root(parent, s) : kNone;  // no union runs any more: what a lane finds IS the root
+  if (live) root[s] = r;
+  tally_root(r, live ? order[s] : kNone, size, min_index);
 }
 
-// the smallest member of every kept component is flagged and remembers its root
+// The smallest member of every kept component is flagged and remembers its root.  Ids are sorted positions (clusters, DBSCAN) or buffer
+// indices (regions); only a root has root[id] == id.  DBSCAN keeps everything: min_size 1, max_size all ones.
 __global__ __launch_bounds__(kBlock) void cluster_flag_kernel(const uint32_t* __restrict__ root, const uint32_t* __restrict__ size, const uint32_t* __restrict__ min_index,
-                                                              uint32_t nf, unsigned long long min_size, unsigned long long max_size, uint32_t* __restrict__ flags,
-                                                              uint32_t* __restrict__ root_at, Record* __restrict__ rec) {
+                                                              uint32_t n_ids, unsigned long long min_size, unsigned long long max_size, uint32_t* __restrict__ flags,
+                                                              uint32_t* __restrict__ root_at, unsigned long long* __restrict__ n_labelled) {
   const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= nf || root[s] != s) return;
+  if (s >= n_ids || root[s] != s) return;
   const unsigned long long sz = size[s];
   if (sz < min_size || sz > max_size) return;
   flags[min_index[s]] = 1;
   root_at[min_index[s]] = s;
-  atomicAdd(&rec->clustered, sz);
+  atomicAdd(n_labelled, sz);
 }
 
 __global__ __launch_bounds__(kBlock) void cluster_list_kernel(const uint32_t* __restrict__ flags, const unsigned long long* __restrict__ offsets,
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void cluster_label_kernel(const uint32_t* _
                                                                uint64_t n, uint32_t nf, uint32_t* __restrict__ labels) {
   const uint64_t s = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= n) return;
-  labels[order[s]] = s < nf ? rank_of_root[root[s]] : kNone;  // (the non-finite points sorted behind the finite ones)
+  labels[order[s]] = s < nf ? rank_of_root[root[s]] : kNone;  // (the non-finite points sorted behind the finite ones; a dropped root: all ones)
 }
 
 __global__ __launch_bounds__(kBlock) void cluster_mask_kernel(const uint32_t* __restrict__ labels, uint64_t n, uint32_t first, uint32_t count, uint8_t* __restrict__ mask) {
@@ -217,14 +212,18 @@ bool cluster_components(const Positions& pos, const ClusterGrid& g, double t2, c
   return launched();
 }
 
-bool cluster_flag_kept(uint32_t* parent, const uint32_t* order, uint64_t n, uint32_t nf, uint64_t min_size, uint64_t max_size, uint32_t* root, uint32_t* size,
-                       uint32_t* min_index, uint32_t* flags, uint32_t* root_at, ClusterRecord* rec, hipStream_t stream) {
-  if (hipMemsetAsync(size, 0, (size_t)nf * sizeof(uint32_t), stream) != hipSuccess || hipMemsetAsync(min_index, 0xFF, (size_t)nf * sizeof(uint32_t), stream) != hipSuccess ||
-      hipMemsetAsync(flags, 0, (size_t)(n + 1) * sizeof(uint32_t), stream) != hipSuccess)  // (one flag more: the scan's last offset is the total)
+bool cluster_flatten(uint32_t* parent, const uint32_t* order, uint32_t nf, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream) {
+  if (hipMemsetAsync(size, 0, (size_t)nf * sizeof(uint32_t), stream) != hipSuccess || hipMemsetAsync(min_index, 0xFF, (size_t)nf * sizeof(uint32_t), stream) != hipSuccess)
     return false;
   hipLaunchKernelGGL(cluster_flatten_kernel, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, parent, order, nf, root, size, min_index);
-  hipLaunchKernelGGL(cluster_flag_kernel, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, (const uint32_t*)root, (const uint32_t*)size, (const uint32_t*)min_index, nf,
-                     (unsigned long long)min_size, (unsigned long long)max_size, flags, root_at, rec);
+  return launched();
+}
+
+bool cluster_flag_kept(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint64_t n, uint32_t n_ids, uint64_t min_size, uint64_t max_size,
+                       uint32_t* flags, uint32_t* root_at, unsigned long long* n_labelled, hipStream_t stream) {
+  if (hipMemsetAsync(flags, 0, (size_t)(n + 1) * sizeof(uint32_t), stream) != hipSuccess) return false;  // (one flag more: the scan's last offset is the total)
+  hipLaunchKernelGGL(cluster_flag_kernel, dim3(blocks_of(n_ids, kBlock)), dim3(kBlock), 0, stream, root, size, min_index, n_ids, (unsigned long long)min_size,
+                     (unsigned long long)max_size, flags, root_at, n_labelled);
   return launched();
 }
 
@@ -234,11 +233,15 @@ bool cluster_list_kept(const uint32_t* flags, const unsigned long long* offsets,
   return launched();
 }
 
-bool cluster_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* order, const uint32_t* root, uint64_t n, uint32_t nf,
-                    uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, hipStream_t stream) {
-  if (nf && hipMemsetAsync(rank_of_root, 0xFF, (size_t)nf * sizeof(uint32_t), stream) != hipSuccess) return false;
+bool cluster_ranks(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, uint32_t n_ids, uint32_t* rank_of_root, unsigned long long* sizes,
+                   hipStream_t stream) {
+  if (hipMemsetAsync(rank_of_root, 0xFF, (size_t)n_ids * sizeof(uint32_t), stream) != hipSuccess) return false;
   if (kept) hipLaunchKernelGGL(cluster_rank_kernel, dim3(blocks_of(kept, kBlock)), dim3(kBlock), 0, stream, sorted_keys, sorted_roots, kept, rank_of_root, sizes);
-  hipLaunchKernelGGL(cluster_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, order, root, (const uint32_t*)rank_of_root, n, nf, labels);
+  return launched();
+}
+
+bool cluster_labels(const uint32_t* order, const uint32_t* root, const uint32_t* rank_of_root, uint64_t n, uint32_t nf, uint32_t* labels, hipStream_t stream) {
+  hipLaunchKernelGGL(cluster_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, order, root, rank_of_root, n, nf, labels);
   return launched();
 }
 

@@ -1,11 +1,11 @@
 // pst_euclidean_clusters / pst_cluster_mask_device / pst_cluster_kernel_shape: argument checks, the scratch layout and the order of the
 // launches of clusters.hip (where the definitions and the argument for the grid's margin are; the grid is cluster_grid.hpp's, the index build
-// cluster_index.hpp's).
+// cluster_index.hpp's, the numbering and the copies to the outputs cluster_numbering.hpp's).
 #include <cmath>
 #include <cstring>
 
 #include "cluster_index.hpp"
-#include "phase_events.hpp"
+#include "cluster_numbering.hpp"
 
 using namespace pst;
 
@@ -115,31 +115,14 @@ int pst_euclidean_clusters(const pst_buffer* b, double tolerance, uint64_t min_s
   const auto [list_keys, list_roots] = ix.halves(ix.keys_a);
   const auto [sorted_keys, sorted_roots] = ix.halves(ix.keys_b);
   uint32_t* rank_of_root = ix.vals_a;
-  if (!pstk::cluster_flag_kept(parent, order, n, nf, min_size, max_size, root, size, min_index, flags, root_at, rec, s)) throw hip_failure("cluster flatten launch failed: ");
-  size_t bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, n + 1, s));
-  if (!pstk::cluster_list_kept(flags, offsets, root_at, size, n, list_keys, list_roots, s)) throw hip_failure("cluster list launch failed: ");
-  unsigned long long kept = 0;
-  pstk::ClusterRecord r{};  // (its `clustered`)
-  PST_HIP_CHECK(hipMemcpyAsync(&kept, offsets + n, sizeof(kept), hipMemcpyDeviceToHost, s));
-  PST_HIP_CHECK(hipMemcpyAsync(&r, rec, sizeof(r), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  // one STABLE sort on 0xFFFFFFFF - size: descending size, and equal sizes keep the list's order, ascending smallest member
-  bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, list_keys, sorted_keys, list_roots, sorted_roots, (size_t)kept, 32, s));
-  unsigned long long* sizes_dev = offsets;  // (the scan's result has been used up)
-  if (!pstk::cluster_labels(sorted_keys, sorted_roots, (uint32_t)kept, order, root, n, nf, rank_of_root, sizes_dev, labels_dev, s))
-    throw hip_failure("cluster label launch failed: ");
+  if (!pstk::cluster_flatten(parent, order, nf, root, size, min_index, s)) throw hip_failure(who + ": flatten launch failed: ");
+  // (the two counters: the record's finite_count, which nobody reads again, and its `clustered`, zero since the bounds pass)
+  const NumberingArrays arrays{root, size, min_index, flags, root_at, list_keys, list_roots, sorted_keys, sorted_roots, rank_of_root, offsets, &rec->finite_count, tmp, tmp_bytes};
+  const Numbered numbered = number_kept(arrays, n, nf, min_size, max_size, s, who);
+  if (!pstk::cluster_labels(order, root, rank_of_root, n, nf, labels_dev, s)) throw hip_failure(who + ": label launch failed: ");
   events.mark(3, s);
-  const bool sizes_fit = kept <= sizes_capacity;
-  if (sizes && sizes_fit && kept) PST_HIP_CHECK(hipMemcpyAsync(sizes, sizes_dev, (size_t)kept * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (!labels_on_device) PST_HIP_CHECK(hipMemcpyAsync(labels, labels_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  events.read();
-  *n_clusters = kept;
-  *n_clustered = r.clustered;
-  if (sizes && !sizes_fit)
-    throw Error(PST_ERR_RANGE, who + ": " + std::to_string(kept) + " clusters do not fit the size array of " + std::to_string(sizes_capacity));
+  finish_numbered(numbered, NumberedOutputs{labels_on_device, labels, labels_dev, nullptr, nullptr, sizes, sizes_capacity, n_clusters, nullptr, n_clustered}, n, events, s, who,
+                  "clusters");
   PST_API_END
 }
 

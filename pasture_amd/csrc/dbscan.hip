@@ -9,14 +9,16 @@
 //             binary searches of the sorted keys (the walk of sample.hip's decision kernel).  The lane counts the candidates that pass the
 //             predicate -- itself among them -- and stops when the count reaches min_points: core[s] = 1.  It also sets parent[s] = s.
 //   link      the cluster traversal restricted to core points: the five rows that hold candidates of lower id, unite(s, c) only when both are
-//             core and neighbours.  A lane that is not core returns at once.  The union-find is that of clusters.hip (grid_index_device.hpp).
+//             core and neighbours.  A lane that is not core returns at once.  The union-find is that of clusters.hip.
 //   border    launched behind the link kernel, so roots are final and nothing is united any more.  A core lane looks up its root.  A lane that
 //             is not core walks the nine rows for core neighbours and keeps the smallest (d2, buffer index); it takes that core point's root,
-//             or "none" without one.  Every labelled lane adds to size[root] and folds its buffer index into min_index[root]: integer atomics,
-//             one pair per wave and root for the first few roots of a wave (a cluster of most of the cloud is one address).
-//   number    the clusters' numbering: flag the smallest member of every cluster, exclusive scan, list, one stable sort on 0xFFFFFFFF - size,
-//             ranks back to the roots, labels and core flags scattered to buffer order.
+//             or "none" without one.  Every labelled lane adds to size[root] and folds its buffer index into min_index[root]: the wave-folded
+//             tally of grid_index_device.hpp (a cluster of most of the cloud is one address).
+//   number    the clusters' numbering with a filter that keeps everything (cluster_numbering.hpp; the flag, list and rank kernels are those
+//             of clusters.hip), then labels and core flags scattered to buffer order by the one kernel of the numbering that is DBSCAN's own.
 //
+// The cell of a key, the stencil rows, the binary search, the predicate, the union-find and the tally are grid_index_device.hpp's, shared with
+// clusters.hip and sample.hip; the row loops are written out here (why: there).
 // Lanes of a wave are neighbours in the sorted order: in all three kernels they search the same key ranges and read the same candidates.  No
 // lane ever waits for another lane's write, and there is no floating-point atomic: sizes are integer sums, the border choice is a minimum over
 // a set that does not depend on the order it is walked in.
@@ -29,30 +31,10 @@ using namespace pstd;
 namespace {
 
 constexpr uint32_t kP = pstk::kDbscanPointsPerBlock;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kFoldRounds = 4;  // distinct roots per wave whose members are folded in the wave before the border kernel's atomics
+constexpr uint32_t kNone = kNoRoot;
 static_assert(kP == kBlock, "one lane per point");
 
 using Grid = pstk::ClusterGrid;
-
-// the cell of a sorted key and the clamped x range of its stencil
-struct Cell { uint32_t cx, cy, cz, x0, x1; };
-__device__ __forceinline__ Cell cell_of_key(unsigned long long key, const Grid& g) {
-  const uint32_t bx = g.bits[0], by = g.bits[1];
-  Cell c;
-  c.cx = (uint32_t)(key & ((1ull << bx) - 1));
-  c.cy = (uint32_t)((key >> bx) & ((1ull << by) - 1));
-  c.cz = (uint32_t)(key >> (bx + by));
-  c.x0 = c.cx > 0 ? c.cx - 1 : 0;
-  c.x1 = c.cx + 1 < g.dim[0] ? c.cx + 1 : c.cx;
-  return c;
-}
-// row r of the nine (r / 3 - 1 in z, r % 3 - 1 in y): false when it lies outside the grid, else the key of its cell x = 0
-__device__ __forceinline__ bool stencil_row(const Cell& c, const Grid& g, int dz, int dy, unsigned long long& row) {
-  if ((dz < 0 && c.cz == 0) || (dz > 0 && c.cz + 1 >= g.dim[2]) || (dy < 0 && c.cy == 0) || (dy > 0 && c.cy + 1 >= g.dim[1])) return false;
-  row = ((unsigned long long)(c.cz + dz) << (g.bits[0] + g.bits[1])) | ((unsigned long long)(c.cy + dy) << g.bits[0]);
-  return true;
-}
 
 // ---- count ------------------------------------------------------------------------------------------------------------------------------------
 // min_points <= nf (the host answers a larger one itself), so it fits 32 bits
@@ -71,10 +53,8 @@ __global__ __launch_bounds__(kBlock) void dbscan_count_kernel(const unsigned lon
       if (!stencil_row(cell, g, r / 3 - 1, r % 3 - 1, row)) continue;
       const uint32_t first = lower_bound(keys, nf, row | cell.x0);
       const uint32_t last = lower_bound(keys, nf, (row | cell.x1) + 1);
-      for (uint32_t c = first; c < last && count < min_points; ++c) {  // (c == s passes: a point is its own neighbour)
-        const double dx = xs[c] - px, dy = ys[c] - py, dz = zs[c] - pz;
-        if ((dx * dx + dy * dy) + dz * dz <= e2) ++count;
-      }
+      for (uint32_t c = first; c < last && count < min_points; ++c)  // (c == s passes: a point is its own neighbour)
+        if (squared_distance(xs[c], ys[c], zs[c], px, py, pz) <= e2) ++count;
     }
     is_core = count >= min_points;
     core[s] = is_core ? 1 : 0;
@@ -99,11 +79,8 @@ __global__ __launch_bounds__(kBlock) void dbscan_link_kernel(const unsigned long
     if (!stencil_row(cell, g, r < 3 ? -1 : 0, r < 3 ? r - 1 : r - 4, row)) continue;
     const uint32_t first = lower_bound(keys, s, row | cell.x0);
     const uint32_t last = r == 4 ? s : lower_bound(keys, s, (row | cell.x1) + 1);  // (keys below s only: every candidate has a lower id)
-    for (uint32_t c = first; c < last; ++c) {
-      if (!core[c]) continue;
-      const double dx = xs[c] - px, dy = ys[c] - py, dz = zs[c] - pz;
-      if ((dx * dx + dy * dy) + dz * dz <= e2) unite(parent, s, c);
-    }
+    for (uint32_t c = first; c < last; ++c)
+      if (core[c] && squared_distance(xs[c], ys[c], zs[c], px, py, pz) <= e2) unite(parent, s, c);
   }
 }
 
@@ -113,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void dbscan_border_kernel(const unsigned lo
                                                                uint32_t nf, Grid g, double e2, uint32_t* parent, uint32_t* __restrict__ root, uint32_t* size,
                                                                uint32_t* min_index) {
   const uint32_t s = blockIdx.x * kP + threadIdx.x;
-  const bool live = s < nf;  // (no lane leaves before the wave-wide fold at the end)
+  const bool live = s < nf;  // (no lane leaves before the wave-wide tally at the end)
   uint32_t member = live ? s : kNone;  // the core point whose cluster s joins
   if (live && !core[s]) {
     const Cell cell = cell_of_key(keys[s], g);
@@ -129,8 +106,7 @@ __global__ __launch_bounds__(kBlock) void dbscan_border_kernel(const unsigned lo
       const uint32_t last = lower_bound(keys, nf, (row | cell.x1) + 1);
       for (uint32_t c = first; c < last; ++c) {
         if (!core[c]) continue;
-        const double dx = xs[c] - px, dy = ys[c] - py, dz = zs[c] - pz;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        const double d2 = squared_distance(xs[c], ys[c], zs[c], px, py, pz);
         if (!(d2 <= e2) || d2 > best_d2) continue;
         const uint32_t index = order[c];
         if (d2 < best_d2 || index < best_index) {
@@ -143,58 +119,10 @@ __global__ __launch_bounds__(kBlock) void dbscan_border_kernel(const unsigned lo
   }
   const uint32_t r = member == kNone ? kNone : find_root(parent, member);  // no union runs any more: what a lane finds IS the root
   if (live) root[s] = r;
-  // Lanes of a wave are neighbours in the sorted order and mostly share a root, and a cluster that holds most of the cloud would take one
-  // atomic per point on ONE address.  So the lanes that share the root of the first pending lane fold their count and their smallest buffer
-  // index in the wave and send one pair of atomics; after kFoldRounds distinct roots the lanes still pending send their own.  Integer sums
-  // and minima: the result does not depend on the grouping.
-  const uint32_t mine = r != kNone ? order[s] : kNone;
-  bool pending = r != kNone;
-#pragma unroll 1
-  for (uint32_t round = 0; round < kFoldRounds; ++round) {
-    const unsigned long long todo = __ballot(pending);
-    if (!todo) break;  // (wave-uniform)
-    const int leader = __builtin_ctzll(todo);
-    const uint32_t r0 = (uint32_t)__shfl((int)r, leader, 64);
-    const bool same = pending && r == r0;
-    const uint32_t members = (uint32_t)__builtin_popcountll(__ballot(same));
-    uint32_t lowest = same ? mine : kNone;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const uint32_t other = shfl_xor_any(lowest, off);
-      lowest = other < lowest ? other : lowest;
-    }
-    if ((int)(threadIdx.x & 63) == leader) {
-      atomicAdd(size + r0, members);
-      atomicMin(min_index + r0, lowest);
-    }
-    pending = pending && !same;
-  }
-  if (pending) {
-    atomicAdd(size + r, 1u);
-    atomicMin(min_index + r, mine);
-  }
+  tally_root(r, r != kNone ? order[s] : kNone, size, min_index);
 }
 
-// ---- numbering ----------------------------------------------------------------------------------------------------------------------------------
-// the smallest member of every cluster is flagged and remembers its root (a root is a core point, and only a root has root[s] == s)
-__global__ __launch_bounds__(kBlock) void dbscan_flag_kernel(const uint32_t* __restrict__ root, const uint32_t* __restrict__ size, const uint32_t* __restrict__ min_index,
-                                                             uint32_t nf, uint32_t* __restrict__ flags, uint32_t* __restrict__ root_at,
-                                                             unsigned long long* __restrict__ n_labelled) {
-  const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-  if (s >= nf || root[s] != s) return;
-  flags[min_index[s]] = 1;
-  root_at[min_index[s]] = s;
-  atomicAdd(n_labelled, (unsigned long long)size[s]);
-}
-
-__global__ __launch_bounds__(kBlock) void dbscan_rank_kernel(const uint32_t* __restrict__ sorted_keys, const uint32_t* __restrict__ sorted_roots, uint32_t clusters,
-                                                             uint32_t* __restrict__ rank_of_root, unsigned long long* __restrict__ sizes) {
-  const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-  if (c >= clusters) return;
-  rank_of_root[sorted_roots[c]] = c;
-  sizes[c] = kNone - sorted_keys[c];
-}
-
+// ---- labels (the flag, list and rank kernels of the numbering are the clusters': clusters.hip) ------------------------------------------------------
 // labels and core flags to buffer order; core_out is nullable
 __global__ __launch_bounds__(kBlock) void dbscan_label_kernel(const uint32_t* __restrict__ order, const uint32_t* __restrict__ root, const uint32_t* __restrict__ rank_of_root,
                                                               const uint8_t* __restrict__ core, uint64_t n, uint32_t nf, uint32_t* __restrict__ labels,
@@ -235,17 +163,9 @@ bool dbscan_border(const unsigned long long* sorted_keys, const double* xs, cons
   return launched();
 }
 
-bool dbscan_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint64_t n, uint32_t nf, uint32_t* flags, uint32_t* root_at,
-                 unsigned long long* n_labelled, hipStream_t stream) {
-  if (hipMemsetAsync(flags, 0, (size_t)(n + 1) * sizeof(uint32_t), stream) != hipSuccess) return false;  // (one flag more: the scan's last offset is the total)
-  hipLaunchKernelGGL(dbscan_flag_kernel, dim3(blocks_of(nf, kBlock)), dim3(kBlock), 0, stream, root, size, min_index, nf, flags, root_at, n_labelled);
-  return launched();
-}
-
-bool dbscan_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t clusters, const uint32_t* order, const uint32_t* root, const uint8_t* core, uint64_t n,
-                   uint32_t nf, uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, uint8_t* core_out, hipStream_t stream) {
-  if (clusters) hipLaunchKernelGGL(dbscan_rank_kernel, dim3(blocks_of(clusters, kBlock)), dim3(kBlock), 0, stream, sorted_keys, sorted_roots, clusters, rank_of_root, sizes);
-  hipLaunchKernelGGL(dbscan_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, order, root, (const uint32_t*)rank_of_root, core, n, nf, labels, core_out);
+bool dbscan_labels(const uint32_t* order, const uint32_t* root, const uint32_t* rank_of_root, const uint8_t* core, uint64_t n, uint32_t nf, uint32_t* labels,
+                   uint8_t* core_out, hipStream_t stream) {
+  hipLaunchKernelGGL(dbscan_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, order, root, rank_of_root, core, n, nf, labels, core_out);
   return launched();
 }
 

@@ -1,11 +1,12 @@
 // pst_dbscan / pst_dbscan_kernel_shape / pst_dbscan_phase_times: argument checks, the scratch layout and the order of the launches of
 // dbscan.hip (where the pipeline is laid out; the definitions are in include/pasture_amd.h, the argument for the grid's margin at the head
-// of clusters.hip; the grid is cluster_grid.hpp's, the index build cluster_index.hpp's).
+// of clusters.hip; the grid is cluster_grid.hpp's, the index build cluster_index.hpp's, the numbering and the copies to the outputs
+// cluster_numbering.hpp's).
 #include <cmath>
 #include <cstring>
 
 #include "cluster_index.hpp"
-#include "phase_events.hpp"
+#include "cluster_numbering.hpp"
 
 using namespace pst;
 
@@ -117,34 +118,11 @@ int pst_dbscan(const pst_buffer* b, double eps, uint64_t min_points, uint32_t* l
   const auto [sorted_keys, sorted_roots] = ix.halves(ix.keys_b);
   uint32_t* rank_of_root = ix.halves(ys).first;
   const auto [root_at, flags] = ix.halves(zs);
-  if (!pstk::dbscan_flag(root, size, min_index, n, nf, flags, root_at, counts_dev + 1, s)) throw hip_failure(who + ": flag launch failed: ");
-  size_t bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, n + 1, s));
-  if (!pstk::cluster_list_kept(flags, offsets, root_at, size, n, list_keys, list_roots, s)) throw hip_failure(who + ": list launch failed: ");
-  unsigned long long clusters = 0, counted[2] = {0, 0};
-  PST_HIP_CHECK(hipMemcpyAsync(&clusters, offsets + n, sizeof(clusters), hipMemcpyDeviceToHost, s));
-  PST_HIP_CHECK(hipMemcpyAsync(counted, counts_dev, sizeof(counted), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  // one STABLE sort on 0xFFFFFFFF - size: descending size, and equal sizes keep the list's order, ascending smallest member
-  bytes = tmp_bytes;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, list_keys, sorted_keys, list_roots, sorted_roots, (size_t)clusters, 32, s));
-  unsigned long long* sizes_dev = offsets;  // (the scan's result has been used up)
-  if (!pstk::dbscan_labels(sorted_keys, sorted_roots, (uint32_t)clusters, order, root, core_sorted, n, nf, rank_of_root, sizes_dev, labels_dev, core_dev, s))
-    throw hip_failure(who + ": label launch failed: ");
+  const NumberingArrays arrays{root, size, min_index, flags, root_at, list_keys, list_roots, sorted_keys, sorted_roots, rank_of_root, offsets, counts_dev, tmp, tmp_bytes};
+  const Numbered numbered = number_kept(arrays, n, nf, 1, UINT64_MAX, s, who);  // (there is no size filter)
+  if (!pstk::dbscan_labels(order, root, rank_of_root, core_sorted, n, nf, labels_dev, core_dev, s)) throw hip_failure(who + ": label launch failed: ");
   events.mark(4, s);
-  const bool sizes_fit = clusters <= sizes_capacity;
-  if (sizes && sizes_fit && clusters) PST_HIP_CHECK(hipMemcpyAsync(sizes, sizes_dev, (size_t)clusters * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (!on_device) {
-    PST_HIP_CHECK(hipMemcpyAsync(labels, labels_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (core) PST_HIP_CHECK(hipMemcpyAsync(core, core_dev, n, hipMemcpyDeviceToHost, s));
-  }
-  stream_sync(s);
-  events.read();
-  counts[0] = clusters;
-  counts[1] = counted[0];
-  counts[2] = counted[1];
-  if (sizes && !sizes_fit)
-    throw Error(PST_ERR_RANGE, who + ": " + std::to_string(clusters) + " clusters do not fit the size array of " + std::to_string(sizes_capacity));
+  finish_numbered(numbered, NumberedOutputs{on_device, labels, labels_dev, core, core_dev, sizes, sizes_capacity, counts, counts + 1, counts + 2}, n, events, s, who, "clusters");
   PST_API_END
 }
 

@@ -224,7 +224,7 @@ bool geometric_features(const Positions& pos, uint32_t k, const uint32_t* knn_de
 constexpr uint32_t kClusterPointsPerBlock = 256;  // points one workgroup of the traversal kernel owns, one lane each
 constexpr uint32_t kClusterTilePoints = 0;        // points of an LDS candidate tile: none, the candidates are read from the sorted arrays
 // the device-side record of one call (64 bytes): the AABB of the finite points in the order-preserving integer encoding, their number, the
-// points that carry a label
+// points that carry a label (the last two in this order: they are the two counters of the clusters' numbering, cluster_numbering.hpp)
 struct ClusterRecord { unsigned long long min_ordered[3], max_ordered[3], finite_count, clustered; };
 double cluster_decode_ordered(unsigned long long v);
 // (ClusterGrid: cluster_grid.hpp)
@@ -235,16 +235,22 @@ bool cluster_keys(const Positions& pos, const ClusterGrid& g, unsigned long long
 // (of `pos` only base and stride are used: the gather reads the nf points `order` names)
 bool cluster_components(const Positions& pos, const ClusterGrid& g, double t2, const unsigned long long* sorted_keys, const uint32_t* order, uint32_t nf, double* xs,
                         double* ys, double* zs, uint32_t* parent, hipStream_t stream, hipEvent_t gathered = nullptr);
-// root, size and smallest buffer index per component; flags[i] = 1 and root_at[i] = root where i is the smallest member of a kept component
-// (flags: n + 1 elements, the last one 0); the record's `clustered`
-bool cluster_flag_kept(uint32_t* parent, const uint32_t* order, uint64_t n, uint32_t nf, uint64_t min_size, uint64_t max_size, uint32_t* root, uint32_t* size,
-                       uint32_t* min_index, uint32_t* flags, uint32_t* root_at, ClusterRecord* rec, hipStream_t stream);
+// root[s], and points and smallest buffer index per root (both set up here; the wave-folded tally of grid_index_device.hpp)
+bool cluster_flatten(uint32_t* parent, const uint32_t* order, uint32_t nf, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream);
+// The numbering, for the clusters, DBSCAN and the regions alike (cluster_numbering.hpp runs the three in order).  n_ids ids -- sorted positions
+// or buffer indices -- carry roots; only a root has root[id] == id; min_index names one of the buffer's n points.
+// flags[i] = 1 and root_at[i] = root where i is the smallest member of a component of min_size .. max_size points (flags: n + 1 elements, set up
+// here, the last one 0); *n_labelled (zeroed) += the kept sizes
+bool cluster_flag_kept(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint64_t n, uint32_t n_ids, uint64_t min_size, uint64_t max_size,
+                       uint32_t* flags, uint32_t* root_at, unsigned long long* n_labelled, hipStream_t stream);
 // offsets = exclusive sum of flags: list_keys[offsets[i]] = 0xFFFFFFFF - size, list_roots[offsets[i]] = root of every flagged i
 bool cluster_list_kept(const uint32_t* flags, const unsigned long long* offsets, const uint32_t* root_at, const uint32_t* size, uint64_t n, uint32_t* list_keys,
                        uint32_t* list_roots, hipStream_t stream);
-// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[order[s]] = rank of s's root, 0xFFFFFFFF without one
-bool cluster_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* order, const uint32_t* root, uint64_t n, uint32_t nf,
-                    uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, hipStream_t stream);
+// the list after the stable sort: rank_of_root = 0xFFFFFFFF for all n_ids, then c for root sorted_roots[c]; sizes[c]
+bool cluster_ranks(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, uint32_t n_ids, uint32_t* rank_of_root, unsigned long long* sizes,
+                   hipStream_t stream);
+// labels[order[s]] = rank of s's root (0xFFFFFFFF: dropped), 0xFFFFFFFF for the non-finite points
+bool cluster_labels(const uint32_t* order, const uint32_t* root, const uint32_t* rank_of_root, uint64_t n, uint32_t nf, uint32_t* labels, hipStream_t stream);
 bool cluster_mask(const uint32_t* labels, uint64_t n, uint32_t first_cluster, uint32_t cluster_count, uint8_t* mask, hipStream_t stream);
 
 // Ground classification by the progressive morphological filter (pmf.hip; the schedule, the grid and the order of the passes are in pmf_api.cpp).
@@ -409,17 +415,14 @@ bool dbscan_count(const unsigned long long* sorted_keys, const double* xs, const
 bool dbscan_link(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, const uint8_t* core, uint32_t nf, const ClusterGrid& g,
                  double e2, uint32_t* parent, hipStream_t stream);
 // behind dbscan_link: root[s] = the root of a core point / of the core neighbour of smallest (d2, buffer index) / 0xFFFFFFFF for noise; points
-// per root and the smallest buffer index per root (both set up here)
+// per root and the smallest buffer index per root (both set up here).  The numbering from there is the clusters' (cluster_flag_kept ..
+// cluster_ranks above, a filter that keeps everything).
 bool dbscan_border(const unsigned long long* sorted_keys, const double* xs, const double* ys, const double* zs, const uint8_t* core, const uint32_t* order, uint32_t nf,
                    const ClusterGrid& g, double e2, uint32_t* parent, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream);
-// flags[i] = 1 and root_at[i] = root where i is the smallest member of a cluster (flags: n + 1 elements, the last one 0); *n_labelled
-// (zeroed) += the sizes.  cluster_list_kept takes it from there.
-bool dbscan_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint64_t n, uint32_t nf, uint32_t* flags, uint32_t* root_at,
-                 unsigned long long* n_labelled, hipStream_t stream);
-// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[order[s]] = rank of root[s], 0xFFFFFFFF without one;
-// core_out[order[s]] = core[s], 0 for the non-finite points (core_out nullable)
-bool dbscan_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t clusters, const uint32_t* order, const uint32_t* root, const uint8_t* core, uint64_t n,
-                   uint32_t nf, uint32_t* rank_of_root, unsigned long long* sizes, uint32_t* labels, uint8_t* core_out, hipStream_t stream);
+// behind cluster_ranks: labels[order[s]] = rank of root[s], 0xFFFFFFFF without one; core_out[order[s]] = core[s], 0 for the non-finite points
+// (core_out nullable)
+bool dbscan_labels(const uint32_t* order, const uint32_t* root, const uint32_t* rank_of_root, const uint8_t* core, uint64_t n, uint32_t nf, uint32_t* labels,
+                   uint8_t* core_out, hipStream_t stream);
 
 // Region growing over neighbour lists (region.hip; the checks, the scratch and the order of the launches are in region_api.cpp).  The seams
 // (pst_region_kernel_shape):
@@ -433,17 +436,12 @@ bool region_classify(const double* normals, const double* curvature, double curv
 bool region_link(const Positions& pos, uint32_t k, const uint32_t* knn, const double* normals, const uint8_t* state, double min_abs_cos, double max_distance,
                  uint32_t* parent, hipStream_t stream);
 // behind region_link: root[i] = the root of a smooth point / of the first agreeing smooth slot of a rim point / 0xFFFFFFFF; points per root
-// and the smallest index per root (both set up here)
+// and the smallest index per root (both set up here).  The numbering from there is the clusters' (cluster_flag_kept .. cluster_ranks above,
+// ids = buffer indices).
 bool region_attach(const Positions& pos, uint32_t k, const uint32_t* knn, const double* normals, const uint8_t* state, double min_abs_cos, double max_distance,
                    uint32_t* parent, uint32_t* root, uint32_t* size, uint32_t* min_index, hipStream_t stream);
-// flags[i] = 1 and root_at[i] = root where i is the smallest member of a region of min_size .. max_size points (flags: n + 1 elements, the
-// last one 0); *n_labelled (zeroed) += the kept sizes.  cluster_list_kept takes it from there.
-bool region_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint32_t n, uint64_t min_size, uint64_t max_size, uint32_t* flags, uint32_t* root_at,
-                 unsigned long long* n_labelled, hipStream_t stream);
-// the list after the stable sort: rank c to root sorted_roots[c], sizes[c]; labels[i] = rank of root[i], 0xFFFFFFFF without a kept one;
-// smooth_out[i] = 1 iff state[i] == 2 (smooth_out nullable)
-bool region_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* root, const uint8_t* state, uint32_t n, uint32_t* rank_of_root,
-                   unsigned long long* sizes, uint32_t* labels, uint8_t* smooth_out, hipStream_t stream);
+// behind cluster_ranks: labels[i] = rank of root[i], 0xFFFFFFFF without a kept one; smooth_out[i] = 1 iff state[i] == 2 (smooth_out nullable)
+bool region_labels(const uint32_t* root, const uint32_t* rank_of_root, const uint8_t* state, uint32_t n, uint32_t* labels, uint8_t* smooth_out, hipStream_t stream);
 
 // Gather by index and the keys of the device sort orders (reorder.hip; the checks, the scratch and the order of the launches are in
 // reorder_api.cpp).  The seams (pst_reorder_kernel_shape):

@@ -13,10 +13,10 @@
 //             and need not be: an edge is found from whichever side names the other.  The union-find is that of clusters.hip.
 //   attach    launched behind link, so roots are final and nothing is united any more.  A smooth lane looks up its own root.  A rim lane walks
 //             its k slots in slot order and takes the root of the first smooth neighbour that counts and agrees, or "none".  Every labelled
-//             lane adds to size[root] and folds its index into min_index[root]: integer atomics, one pair per wave and root for the first
-//             few roots of a wave (a ground plane that holds most of the cloud is one address) -- the fold of dbscan_border_kernel.
-//   number    the clusters' numbering in buffer order: size filter, flag the smallest member of every kept region, exclusive scan, list
-//             (cluster_list_kept), one stable sort on 0xFFFFFFFF - size, ranks back to the roots, labels and the smooth mask.
+//             lane adds to size[root] and folds its index into min_index[root]: the wave-folded tally of grid_index_device.hpp (a ground
+//             plane that holds most of the cloud is one address).
+//   number    the clusters' numbering in buffer order (cluster_numbering.hpp; the flag, list and rank kernels are those of clusters.hip), then
+//             labels and the smooth mask by the one kernel of the numbering that is the regions' own.
 //
 // No lane ever waits for another lane's write, there is no floating-point atomic, and the only retry loop is the union-find's CAS, which
 // strictly descends: sizes are integer sums, the rim choice is "first in slot order", the numbering is a stable sort.
@@ -29,8 +29,7 @@ using namespace pstd;
 namespace {
 
 constexpr uint32_t kThreads = pstk::kRegionThreads;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kFoldRounds = 4;  // distinct roots per wave whose members are folded in the wave before the attach kernel's atomics
+constexpr uint32_t kNone = kNoRoot;
 constexpr uint8_t kInvalid = 0, kRim = 1, kSmooth = 2;
 static_assert(kThreads == kBlock, "the link kernel is written for one kBlock workgroup");
 
@@ -42,8 +41,7 @@ __device__ __forceinline__ bool within(const Pos& pos, uint64_t i, uint64_t j, d
   double qx, qy, qz, px, py, pz;
   load_point(pos, i, qx, qy, qz);
   load_point(pos, j, px, py, pz);
-  const double dx = px - qx, dy = py - qy, dz = pz - qz;
-  return __builtin_sqrt((dx * dx + dy * dy) + dz * dz) <= max_distance;
+  return __builtin_sqrt(squared_distance(px, py, pz, qx, qy, qz)) <= max_distance;
 }
 
 // ---- classify ---------------------------------------------------------------------------------------------------------------------------------
@@ -119,59 +117,10 @@ __global__ __launch_bounds__(kBlock) void region_attach_kernel(Pos pos, uint32_t
   }
   const uint32_t r = member == kNone ? kNone : find_root(parent, member);  // no union runs any more: what a lane finds IS the root
   if (live) root[i] = r;
-  // The lanes that share the root of the first pending lane fold their count and their smallest index in the wave and send one pair of
-  // atomics; after kFoldRounds distinct roots the lanes still pending send their own.  Integer sums and minima: the result does not depend
-  // on the grouping.
-  const uint32_t mine = r != kNone ? i : kNone;
-  bool pending = r != kNone;
-#pragma unroll 1
-  for (uint32_t round = 0; round < kFoldRounds; ++round) {
-    const unsigned long long todo = __ballot(pending);
-    if (!todo) break;  // (wave-uniform)
-    const int leader = __builtin_ctzll(todo);
-    const uint32_t r0 = (uint32_t)__shfl((int)r, leader, 64);
-    const bool same = pending && r == r0;
-    const uint32_t members = (uint32_t)__builtin_popcountll(__ballot(same));
-    uint32_t lowest = same ? mine : kNone;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const uint32_t other = shfl_xor_any(lowest, off);
-      lowest = other < lowest ? other : lowest;
-    }
-    if ((int)(threadIdx.x & 63) == leader) {
-      atomicAdd(size + r0, members);
-      atomicMin(min_index + r0, lowest);
-    }
-    pending = pending && !same;
-  }
-  if (pending) {
-    atomicAdd(size + r, 1u);
-    atomicMin(min_index + r, mine);
-  }
+  tally_root(r, r != kNone ? i : kNone, size, min_index);
 }
 
-// ---- numbering ----------------------------------------------------------------------------------------------------------------------------------
-// the smallest member of every kept region is flagged and remembers its root (a root is a smooth point, and only a root has root[i] == i)
-__global__ __launch_bounds__(kBlock) void region_flag_kernel(const uint32_t* __restrict__ root, const uint32_t* __restrict__ size, const uint32_t* __restrict__ min_index,
-                                                             uint32_t n, unsigned long long min_size, unsigned long long max_size, uint32_t* __restrict__ flags,
-                                                             uint32_t* __restrict__ root_at, unsigned long long* __restrict__ n_labelled) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n || root[i] != i) return;
-  const unsigned long long sz = size[i];
-  if (sz < min_size || sz > max_size) return;
-  flags[min_index[i]] = 1;
-  root_at[min_index[i]] = i;
-  atomicAdd(n_labelled, sz);
-}
-
-__global__ __launch_bounds__(kBlock) void region_rank_kernel(const uint32_t* __restrict__ sorted_keys, const uint32_t* __restrict__ sorted_roots, uint32_t kept,
-                                                             uint32_t* __restrict__ rank_of_root, unsigned long long* __restrict__ sizes) {
-  const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-  if (c >= kept) return;
-  rank_of_root[sorted_roots[c]] = c;
-  sizes[c] = kNone - sorted_keys[c];
-}
-
+// ---- labels (the flag, list and rank kernels of the numbering are the clusters': clusters.hip) ------------------------------------------------------
 // rank_of_root: 0xFFFFFFFF where the root's region was dropped; smooth_out is nullable
 __global__ __launch_bounds__(kBlock) void region_label_kernel(const uint32_t* __restrict__ root, const uint32_t* __restrict__ rank_of_root, const uint8_t* __restrict__ state,
                                                               uint32_t n, uint32_t* __restrict__ labels, uint8_t* __restrict__ smooth_out) {
@@ -212,19 +161,8 @@ bool region_attach(const Positions& pos, uint32_t k, const uint32_t* knn, const 
   return launched();
 }
 
-bool region_flag(const uint32_t* root, const uint32_t* size, const uint32_t* min_index, uint32_t n, uint64_t min_size, uint64_t max_size, uint32_t* flags, uint32_t* root_at,
-                 unsigned long long* n_labelled, hipStream_t stream) {
-  if (hipMemsetAsync(flags, 0, ((size_t)n + 1) * sizeof(uint32_t), stream) != hipSuccess) return false;  // (one flag more: the scan's last offset is the total)
-  hipLaunchKernelGGL(region_flag_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, root, size, min_index, n, (unsigned long long)min_size,
-                     (unsigned long long)max_size, flags, root_at, n_labelled);
-  return launched();
-}
-
-bool region_labels(const uint32_t* sorted_keys, const uint32_t* sorted_roots, uint32_t kept, const uint32_t* root, const uint8_t* state, uint32_t n, uint32_t* rank_of_root,
-                   unsigned long long* sizes, uint32_t* labels, uint8_t* smooth_out, hipStream_t stream) {
-  if (hipMemsetAsync(rank_of_root, 0xFF, (size_t)n * sizeof(uint32_t), stream) != hipSuccess) return false;
-  if (kept) hipLaunchKernelGGL(region_rank_kernel, dim3(blocks_of(kept, kBlock)), dim3(kBlock), 0, stream, sorted_keys, sorted_roots, kept, rank_of_root, sizes);
-  hipLaunchKernelGGL(region_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, root, (const uint32_t*)rank_of_root, state, n, labels, smooth_out);
+bool region_labels(const uint32_t* root, const uint32_t* rank_of_root, const uint8_t* state, uint32_t n, uint32_t* labels, uint8_t* smooth_out, hipStream_t stream) {
+  hipLaunchKernelGGL(region_label_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, root, rank_of_root, state, n, labels, smooth_out);
   return launched();
 }
 

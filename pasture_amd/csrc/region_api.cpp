@@ -1,11 +1,12 @@
 // pst_region_growing_from_knn / pst_region_growing / pst_region_kernel_shape / pst_region_phase_times: argument checks, the scratch layout
 // and the order of the launches of region.hip (where the pipeline is laid out; the definition is in include/pasture_amd.h).  The full call
-// puts the kNN search (knn_checks.hpp) and the feature kernel (features.hip: e3 and the surface variation) in front of it.
+// puts the kNN search (knn_checks.hpp) and the feature kernel (features.hip: e3 and the surface variation) in front of it; the numbering
+// and the copies to the outputs behind it are cluster_numbering.hpp's.
 #include <cmath>
 #include <cstring>
 
+#include "cluster_numbering.hpp"
 #include "knn_checks.hpp"
-#include "phase_events.hpp"
 
 using namespace pst;
 
@@ -69,7 +70,7 @@ struct RegionWork {
   }
 };
 
-// classify + link, attach + numbering: marks events 1 .. 3 (the caller marked 0 in front of whatever it ran itself)
+// classify + link, attach + numbering (number_kept, the label kernel, finish_numbered): marks events 1 .. 3 (the caller marked 0 in front of whatever it ran itself)
 void run_regions(const pstk::Positions& pos, uint32_t k, const uint32_t* d_knn, const double* d_normals, const double* d_curvature, const RegionArgs& a, RegionWork& w,
                  Scratch& scratch, PhaseEvents<3>& events, hipStream_t s, const std::string& who) {
   const uint32_t n = (uint32_t)w.n;
@@ -93,33 +94,12 @@ void run_regions(const pstk::Positions& pos, uint32_t k, const uint32_t* d_knn, 
   events.mark(2, s);
   // ---- rim points, then the bookkeeping
   if (!pstk::region_attach(pos, k, d_knn, d_normals, state, a.min_abs_cos, a.max_distance, parent, root, size, min_index, s)) throw hip_failure(who + ": attach launch failed: ");
-  if (!pstk::region_flag(root, size, min_index, n, a.min_size, a.max_size, flags, root_at, counts_dev + 1, s)) throw hip_failure(who + ": flag launch failed: ");
-  size_t bytes = w.tmp_bytes;
-  PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(tmp, bytes, flags, offsets, w.n + 1, s));
-  if (!pstk::cluster_list_kept(flags, offsets, root_at, size, w.n, list_keys, list_roots, s)) throw hip_failure(who + ": list launch failed: ");
-  unsigned long long kept = 0, counted[2] = {0, 0};
-  PST_HIP_CHECK(hipMemcpyAsync(&kept, offsets + w.n, sizeof(kept), hipMemcpyDeviceToHost, s));
-  PST_HIP_CHECK(hipMemcpyAsync(counted, counts_dev, sizeof(counted), hipMemcpyDeviceToHost, s));
-  stream_sync(s);
-  // one STABLE sort on 0xFFFFFFFF - size: descending size, and equal sizes keep the list's order, ascending smallest member
-  bytes = w.tmp_bytes;
-  if (kept) PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, list_keys, sorted_keys, list_roots, sorted_roots, (size_t)kept, 32, s));
-  unsigned long long* sizes_dev = offsets;  // (the scan's result has been used up)
-  if (!pstk::region_labels(sorted_keys, sorted_roots, (uint32_t)kept, root, state, n, rank_of_root, sizes_dev, labels_dev, smooth_dev, s))
-    throw hip_failure(who + ": label launch failed: ");
+  const NumberingArrays arrays{root, size, min_index, flags, root_at, list_keys, list_roots, sorted_keys, sorted_roots, rank_of_root, offsets, counts_dev, tmp, w.tmp_bytes};
+  const Numbered numbered = number_kept(arrays, w.n, n, a.min_size, a.max_size, s, who);
+  if (!pstk::region_labels(root, rank_of_root, state, n, labels_dev, smooth_dev, s)) throw hip_failure(who + ": label launch failed: ");
   events.mark(3, s);
-  const bool sizes_fit = kept <= a.sizes_capacity;
-  if (a.sizes && sizes_fit && kept) PST_HIP_CHECK(hipMemcpyAsync(a.sizes, sizes_dev, (size_t)kept * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (!on_device) {
-    PST_HIP_CHECK(hipMemcpyAsync(a.labels, labels_dev, w.b4, hipMemcpyDeviceToHost, s));
-    if (a.smooth) PST_HIP_CHECK(hipMemcpyAsync(a.smooth, smooth_dev, w.n, hipMemcpyDeviceToHost, s));
-  }
-  stream_sync(s);
-  events.read();
-  a.counts[0] = kept;
-  a.counts[1] = counted[0];
-  a.counts[2] = counted[1];
-  if (a.sizes && !sizes_fit) throw Error(PST_ERR_RANGE, who + ": " + std::to_string(kept) + " regions do not fit the size array of " + std::to_string(a.sizes_capacity));
+  finish_numbered(numbered, NumberedOutputs{on_device, a.labels, labels_dev, a.smooth, smooth_dev, a.sizes, a.sizes_capacity, a.counts, a.counts + 1, a.counts + 2}, w.n, events,
+                  s, who, "regions");
 }
 
 bool timed() {

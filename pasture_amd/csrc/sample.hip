@@ -8,8 +8,9 @@
 //             the head of clusters.hip carries over word for word, conflicting points are at most one cell apart on every axis), the 64-bit
 //             radix sort, then the positions gathered into sorted order.  From here on a point's id is its SORTED position s < nf.
 //   decide    the hot kernel, one lane per ACTIVE (still undecided) point: all nine (y, z) rows of the 3 x 3 x 3 stencil, each one contiguous
-//             key range [x - 1, x + 1] found by two binary searches of the sorted keys.  Among the conflicting candidates of SMALLER priority
-//             key: a kept one makes the point rejected (stop at the first); otherwise, if none is undecided, the point is kept; otherwise it
+//             key range [x - 1, x + 1] found by two binary searches of the sorted keys (the cell of a key, the rows, the search and the
+//             predicate are grid_index_device.hpp's; DBSCAN's count and border kernels walk the same way).  Among the conflicting candidates
+//             of SMALLER priority key: a kept one makes the point rejected (stop at the first); otherwise, if none is undecided, the point is kept; otherwise it
 //             stays undecided.  A lane sweeps its point kSampleSweepsPerLaunch times at the most.
 //   compact   flags (1 = still undecided, written by the decision kernel) -> exclusive scan -> the next active list; the host reads its length
 //   mask      mask[order[s]] = state[s] == kept for s < nf, 0 for the non-finite points behind them; the kept count
@@ -124,10 +125,7 @@ __global__ __launch_bounds__(kBlock) void sample_decide_kernel(const unsigned lo
   if (t >= m) return;
   if (t == m - 1) flags[m] = 0;
   const uint32_t s = active ? active[t] : t;
-  const unsigned long long key = keys[s];
-  const uint32_t bx = g.bits[0], by = g.bits[1];
-  const uint32_t cx = (uint32_t)(key & ((1ull << bx) - 1)), cy = (uint32_t)((key >> bx) & ((1ull << by) - 1)), cz = (uint32_t)(key >> (bx + by));
-  const uint32_t x0 = cx > 0 ? cx - 1 : 0, x1 = cx + 1 < g.dim[0] ? cx + 1 : cx;
+  const Cell cell = cell_of_key(keys[s], g);
   const double px = xs[s], py = ys[s], pz = zs[s];
   const unsigned long long mine = priority_of(shuffled, seed, order[s]);
   uint8_t st = kUndecided;
@@ -136,17 +134,15 @@ __global__ __launch_bounds__(kBlock) void sample_decide_kernel(const unsigned lo
     bool kept_seen = false, undecided_seen = false;
 #pragma unroll 1
     for (int r = 0; r < 9 && !kept_seen; ++r) {
-      const int dz = r / 3 - 1, dy = r % 3 - 1;
-      if ((dz < 0 && cz == 0) || (dz > 0 && cz + 1 >= g.dim[2]) || (dy < 0 && cy == 0) || (dy > 0 && cy + 1 >= g.dim[1])) continue;
-      const unsigned long long row = ((unsigned long long)(cz + dz) << (bx + by)) | ((unsigned long long)(cy + dy) << bx);
-      const uint32_t first = lower_bound(keys, nf, row | x0);
-      const uint32_t last = lower_bound(keys, nf, (row | x1) + 1);
+      unsigned long long row;
+      if (!stencil_row(cell, g, r / 3 - 1, r % 3 - 1, row)) continue;
+      const uint32_t first = lower_bound(keys, nf, row | cell.x0);
+      const uint32_t last = lower_bound(keys, nf, (row | cell.x1) + 1);
       for (uint32_t c = first; c < last; ++c) {
         if (c == s) continue;
         const uint8_t sc = state_of(state, c);
         if (sc == kRejected) continue;  // a rejected point decides nothing
-        const double dx = xs[c] - px, dy2 = ys[c] - py, dz2 = zs[c] - pz;
-        if (!((dx * dx + dy2 * dy2) + dz2 * dz2 <= r2)) continue;
+        if (!(squared_distance(xs[c], ys[c], zs[c], px, py, pz) <= r2)) continue;
         if (priority_of(shuffled, seed, order[c]) > mine) continue;  // (keys never tie: both orders are injective in the buffer index)
         if (sc == kKept) { kept_seen = true; break; }
         undecided_seen = true;
