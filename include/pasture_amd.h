@@ -1086,6 +1086,70 @@ int pst_geometric_features(const pst_buffer* b, size_t k, double max_distance, u
  * workgroup owns, and its threads.  k outside 1 .. 64 -> PST_ERR_INVALID_ARGUMENT.  Host only. */
 int pst_features_kernel_shape(size_t k, uint32_t* points_per_block, uint32_t* threads);
 
+/* ---- Polygon crop and overlay: point-in-polygon ids and masks ---------------------------------------------------------------------------
+ * What PDAL's filters.crop (polygon, inside or outside) and filters.overlay, and lidR's clip_roi and merge_spatial compute (the reference has
+ * neither): which polygon of a set a point falls in.  The definition, which both kernels and tests/crop_ref.py evaluate exactly:
+ *   polygon set:  P >= 1 polygons; a polygon is one or more rings; a ring is at least 3 vertices (x, y) in f64, all finite, closed
+ *                 implicitly, last vertex to first (a repeated first vertex is allowed and adds only a degenerate edge).  Ring orientation
+ *                 carries no meaning: holes, islands inside holes and self-intersections are all handled by the even-odd rule.
+ *   edges:        an edge with a.y == b.y is dropped; every other edge is stored canonically, lo = the endpoint with the smaller y, hi = the
+ *                 other (an "entry").
+ *   crossing:     a point p with finite p.x and p.y crosses an entry iff lo.y <= p.y and p.y < hi.y and d > 0, where
+ *                 d = (hi.x - lo.x) * (p.y - lo.y) - (p.x - lo.x) * (hi.y - lo.y), evaluated in f64 with one rounding per operation (four
+ *                 subtractions, two products, one subtraction; no FMA).  An infinite or NaN d gives "d > 0" false.  z is ignored, even
+ *                 when it is not finite.
+ *   containment:  p is in a polygon iff it crosses an odd number of that polygon's entries; a point whose x or y is not finite is in no
+ *                 polygon.  id = the smallest polygon index that contains p, or 0xFFFFFFFF (no polygon).  mask = (id != 0xFFFFFFFF); with
+ *                 `outside` the byte-for-byte complement, so an outside crop keeps the points that are not finite.
+ * Consequences: containment is half-open like the raster's cells (of the unit square the left and bottom edges are inside, the right and top
+ * edges outside); two polygons that share an edge evaluate the identical expression for it, whatever direction each ring runs it, so the XOR
+ * of the containments of the cells of a subdivision is the containment of its outline, exactly; for a vertical edge d is
+ * -(p.x - lo.x) * (hi.y - lo.y), whose sign is exact, so axis-aligned rectangles that tile a grid give every point to exactly the cell that
+ * comparisons against the grid lines give.
+ * The result is a function of the set and the points alone: not of the kernel, the number of bands or the storage kind.  Two kernels, one
+ * launch per query: "flat" keeps every entry in LDS and serves sets of at most pst_crop_kernel_shape's flat_max_edges
+ * entries; "banded" walks, per point, the list of the y-band the point is in.  The band directory is built on the host: B equal bands over
+ * the box's [ymin, ymax]; band(y) = clamp(floor((y - ymin) * scale), 0, B - 1), scale = B / (ymax - ymin) rounded once; an entry is listed in
+ * the bands band(lo.y) .. band(hi.y).  Every step of band() is monotone in y, so a point's band lists every entry it can cross, without
+ * any epsilon.
+ * Checks: null arguments and an invalid set are answered before a device is looked for; then PST_ERR_MISSING_ATTRIBUTE when Position3D is not
+ * stored as Vec3f64; an empty buffer is answered on the host; then the device (none: PST_ERR_NO_DEVICE, never a CPU path); 2^32 - 16 points
+ * and more -> PST_ERR_UNSUPPORTED.  Interleaved or columnar, owned, sliced or external, the position at any byte offset.
+ * Cost per point and entry tested: 7 f64 operations and 3 compares; traffic: the 24-byte positions in (z rides along in the same lines),
+ * 1 or 4 bytes out. */
+typedef struct pst_polygon_set pst_polygon_set;
+/* The set, indexed on the host and copied into device memory of its own (36 bytes per entry or directory entry; not the scratch pool).  xy:
+ * the vertices, x and y interleaved, ring after ring; ring r = vertices ring_offsets[r] .. ring_offsets[r + 1] - 1 (n_rings + 1 offsets, from
+ * 0).  polygon_of_ring: n_rings polygon indices, not decreasing from 0 without gaps; NULL = one polygon made of all rings.  bands: B, 0 =
+ * chosen from the number of entries.  kernel: 0 = automatic (flat up to flat_max_edges entries), 1 = flat, 2 = banded.  The caller's arrays
+ * are not read after the call.  PST_ERR_INVALID_ARGUMENT, with the limit named in the message: a ring of fewer than 3 vertices, offsets that
+ * do not start at 0 or decrease, a vertex that is not finite, a polygon_of_ring with a gap, more than 2^24 vertices, more than 2^24 bands,
+ * more than 2^27 directory entries (entries summed over the bands that list them: ask for fewer bands), kernel > 2, flat asked for a set of
+ * more than flat_max_edges entries.  Synchronous. */
+int pst_polygon_set_create(const double* xy, const uint64_t* ring_offsets, size_t n_rings, const uint32_t* polygon_of_ring, uint32_t bands, uint32_t kernel,
+                           pst_polygon_set** out);
+int pst_polygon_set_destroy(pst_polygon_set* set);
+/* What the set was built with (each pointer optional; host only): counts = {polygons, entries, bands, directory entries}, box = {xmin, ymin,
+ * xmax, ymax} over all vertices, *kernel = the kernel taken (1 flat, 2 banded). */
+int pst_polygon_set_info(const pst_polygon_set* set, uint64_t counts[4], double box[4], uint32_t* kernel);
+/* d_ids[i] = the id of point i as defined above: len x uint32 in DEVICE memory.  Stream-ordered on the thread's current stream, nothing is
+ * read back: it can be captured in a graph. */
+int pst_points_in_polygons_device(const pst_polygon_set* set, const pst_buffer* b, uint32_t* d_ids);
+/* d_mask[i] = the mask byte of point i as defined above (outside != 0: the complement): len bytes in DEVICE memory, what
+ * pst_buffer_filter(..., PST_MEM_DEVICE, ...), pst_buffer_filter_into and pst_buffer_filter_into_async take.  count == NULL: stream-ordered,
+ * nothing is read back.  Otherwise *count = the ones of the mask (folded per wave into one device word, integer atomics only), and the call
+ * returns after the stream has finished. */
+int pst_polygon_mask_device(const pst_polygon_set* set, const pst_buffer* b, int outside, uint8_t* d_mask, uint64_t* count);
+/* The companion of pst_buffer_set_u8_where_device for an overlay: the U8 attribute of that name (interleaved or columnar) =
+ * d_values[d_ids[i]] wherever d_ids[i] < n_values; the other points -- 0xFFFFFFFF among them -- keep theirs.  d_ids (len x uint32) and
+ * d_values (n_values bytes) in DEVICE memory.  No such U8 attribute -> PST_ERR_MISSING_ATTRIBUTE.  written == NULL: stream-ordered;
+ * otherwise *written = the points written, after the stream has finished.  An empty buffer and n_values == 0 are answered on the host. */
+int pst_buffer_set_u8_from_ids_device(pst_buffer* b, const char* attribute_name, const uint32_t* d_ids, const uint8_t* d_values, uint32_t n_values, uint64_t* written);
+/* The kernels' seams (tests place their sizes around them; each pointer optional): points per workgroup of the flat kernel and of the banded
+ * one, and the most entries the flat kernel takes -- also the count up to which the automatic choice takes it.  That count is what the
+ * LDS holds: measured at 4, 64, 512 and that many entries, the flat kernel was the faster one every time.  Host only. */
+int pst_crop_kernel_shape(uint32_t* flat_points_per_block, uint32_t* banded_points_per_block, uint32_t* flat_max_edges);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

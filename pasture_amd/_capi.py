@@ -251,6 +251,13 @@ _PRODUCT_SIGNATURES = {
     "invert_order_device": [_P, C.c_uint64, _P],
     "reorder_kernel_shape": [_U32P, _U32P],
     "reorder_phase_times": [_D3],
+    "polygon_set_create": [_D3, _U64P, _SZ, _U32P, C.c_uint32, C.c_uint32, _PP],
+    "polygon_set_destroy": [_P],
+    "polygon_set_info": [_P, _U64P, _D3, _U32P],
+    "points_in_polygons_device": [_P, _P, _P],
+    "polygon_mask_device": [_P, _P, C.c_int, _P, _U64P],
+    "buffer_set_u8_from_ids_device": [_P, C.c_char_p, _P, _P, C.c_uint32, _U64P],
+    "crop_kernel_shape": [_U32P, _U32P, _U32P],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

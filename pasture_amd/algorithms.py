@@ -1451,3 +1451,144 @@ def reorder_phase_times(api=None):
     """(bounds and keys, sort, gather) in milliseconds of this thread's last synchronous gather or sort-order call; zeros unless
     PST_REORDER_TIMES=1 was set when the library first ran one."""
     return _phase_times(api, "reorder_phase_times", 3)
+
+
+# ---- polygon crop and overlay: point-in-polygon ids and masks (include/pasture_amd.h) ----------------------------------------------------------
+
+NO_POLYGON = 0xFFFFFFFF
+_CROP_KERNELS = {"auto": 0, "flat": 1, "banded": 2}
+
+
+def _polygon_arrays(polygons):
+    """`polygons` as the C ABI takes a set: vertices (V, 2) float64, ring offsets (R + 1,) uint64, polygon of every ring (R,) uint32"""
+    rings, polygon_of_ring = [], []
+    for p, polygon in enumerate(polygons):
+        try:
+            a = np.asarray(polygon, dtype=np.float64)
+        except ValueError:  # rings of different lengths
+            a = None
+        parts = [a] if a is not None and a.ndim == 2 else [np.asarray(r, dtype=np.float64) for r in polygon]
+        for ring in parts:
+            if ring.ndim != 2 or ring.shape[1] != 2:
+                raise ValueError("a ring is an (m, 2) array of x and y")
+            rings.append(ring)
+            polygon_of_ring.append(p)
+    if not rings:
+        raise ValueError("a polygon set has at least one polygon")
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in rings])]).astype(np.uint64)
+    return np.ascontiguousarray(np.concatenate(rings)), offsets, np.asarray(polygon_of_ring, dtype=np.uint32)
+
+
+class PolygonSet:
+    """A set of polygons indexed for the point-in-polygon kernels (pst_polygon_set_create), in device memory of its own until destroy().
+    `polygons` is a list of polygons; each is an (m, 2) array of x and y, or a list of such arrays -- outer rings and holes alike: ring
+    orientation carries no meaning, the even-odd rule decides.  bands = 0 chooses the number of y-bands from the set; kernel is "auto",
+    "flat" (every edge in LDS; small sets only) or "banded"."""
+
+    def __init__(self, polygons, bands: int = 0, kernel: str = "auto", api=None):
+        from ._capi import product_api
+        self.api = api or product_api()
+        self._h = None
+        xy, offsets, polygon_of_ring = _polygon_arrays(polygons)
+        h = C.c_void_p()
+        self.api.polygon_set_create(xy.ctypes.data_as(C.POINTER(C.c_double)), _u64(offsets), len(offsets) - 1, polygon_of_ring.ctypes.data_as(C.POINTER(C.c_uint32)), bands,
+                                    _CROP_KERNELS[kernel], C.byref(h))
+        self._h = h
+
+    @property
+    def info(self) -> dict:
+        """polygons, entries (the edges that are not horizontal), bands, directory_entries (entries summed over the bands that list them), the
+        box (xmin, ymin, xmax, ymax) and the kernel taken."""
+        counts, box, kernel = (C.c_uint64 * 4)(), (C.c_double * 4)(), C.c_uint32()
+        self.api.polygon_set_info(self._h, counts, box, C.byref(kernel))
+        return {"polygons": counts[0], "entries": counts[1], "bands": counts[2], "directory_entries": counts[3], "box": tuple(box),
+                "kernel": {1: "flat", 2: "banded"}[kernel.value]}
+
+    def destroy(self) -> None:
+        if self._h is not None and self._h.value:
+            self.api.polygon_set_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class _SetFor:
+    """`polygons` as a PolygonSet: one that is passed in stays the caller's, one built here is destroyed on exit."""
+
+    def __init__(self, polygons, api):
+        self.own = not isinstance(polygons, PolygonSet)
+        self.set = PolygonSet(polygons, api=api) if self.own else polygons
+
+    def __enter__(self):
+        return self.set
+
+    def __exit__(self, *exc):
+        if self.own:
+            self.set.destroy()
+
+
+def points_in_polygons(buffer: _Buffer, polygons, device_ids_ptr: Optional[int] = None):
+    """Per point the smallest index of a polygon of the set that contains it (even-odd rule, half-open like the raster's cells; x and y only),
+    NO_POLYGON = 0xFFFFFFFF without one.  `polygons` is a PolygonSet or what PolygonSet takes.  Returns a numpy uint32 array, or None when
+    the len(buffer) values went to DEVICE memory at device_ids_ptr (stream-ordered then)."""
+    from .layout import PointAttributeDataType as T
+    with _SetFor(polygons, buffer.api) as ps:
+        if device_ids_ptr is not None:
+            buffer.api.points_in_polygons_device(ps._h, buffer._h, C.c_void_p(int(device_ids_ptr) or None))
+            return None
+        ids = _DeviceArray(buffer.api, T.U32, buffer.len())
+        buffer.api.points_in_polygons_device(ps._h, buffer._h, C.c_void_p(ids.ptr or None))
+        return ids.to_numpy()
+
+
+def polygon_mask(buffer: _Buffer, polygons, outside: bool = False, device_mask_ptr: Optional[int] = None):
+    """(mask, count): mask[i] = 1 iff point i is in a polygon of the set -- with `outside` iff it is in none, which keeps the points that are
+    not finite -- and the number of ones.  mask is a numpy uint8 array, or None when the len(buffer) bytes went to DEVICE memory at
+    device_mask_ptr: what filter takes as (ptr, 'device')."""
+    from .layout import PointAttributeDataType as T
+    count = C.c_uint64()
+    with _SetFor(polygons, buffer.api) as ps:
+        if device_mask_ptr is not None:
+            buffer.api.polygon_mask_device(ps._h, buffer._h, int(bool(outside)), C.c_void_p(int(device_mask_ptr) or None), C.byref(count))
+            return None, count.value
+        mask = _DeviceArray(buffer.api, T.U8, buffer.len())
+        buffer.api.polygon_mask_device(ps._h, buffer._h, int(bool(outside)), C.c_void_p(mask.ptr or None), C.byref(count))
+        return mask.to_numpy(), count.value
+
+
+def crop(buffer: _Buffer, polygons, outside: bool = False, out_buffer_type=None):
+    """PDAL's filters.crop with a polygon / lidR's clip_roi: (the points inside the set -- outside it with `outside` -- in buffer order with
+    all their attributes, their number).  Mask and compaction stay in device memory.  `buffer` is columnar (filter is defined on
+    HashMapBuffer)."""
+    with _SetFor(polygons, buffer.api) as ps:
+        return _filter_by_device_mask(buffer, out_buffer_type, lambda p: polygon_mask(buffer, ps, outside, device_mask_ptr=p or 1)[1])
+
+
+def overlay(buffer: _Buffer, attribute: PointAttributeDefinition, polygons, values) -> int:
+    """PDAL's filters.overlay / lidR's merge_spatial: the U8 `attribute` of every point inside a polygon becomes values[id], id the point's
+    polygon; the other points keep theirs, and so does a point whose polygon has no value (id >= len(values)).  In place, on the device.
+    Returns the number of points written."""
+    from .layout import PointAttributeDataType as T
+    values = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
+    n, written = buffer.len(), C.c_uint64()
+    with _SetFor(polygons, buffer.api) as ps:
+        ids, vals = _DeviceArray(buffer.api, T.U32, n), _DeviceArray(buffer.api, T.U8, len(values))
+        if len(values):
+            vals.buffer.set_attribute_range(vals.attribute, range(0, len(values)), values)
+        buffer.api.points_in_polygons_device(ps._h, buffer._h, C.c_void_p(ids.ptr or None))
+        buffer.api.buffer_set_u8_from_ids_device(buffer._h, attribute.name().encode(), C.c_void_p(ids.ptr or None), C.c_void_p(vals.ptr or None), len(values), C.byref(written))
+    return written.value
+
+
+def crop_kernel_shape(api=None) -> dict:
+    """The seams of the point-in-polygon kernels: points per workgroup of the flat and of the banded kernel, and the most entries the flat
+    kernel takes (also where the automatic choice changes over: what the LDS holds; the flat kernel was the faster one at every measured
+    count up to it)."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).crop_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("flat_points_per_block", "banded_points_per_block", "flat_max_edges"), (x.value for x in v)))

@@ -486,4 +486,31 @@ bool reorder_shuffle_keys(uint64_t n, uint64_t seed, unsigned long long* keys, u
 // inverse[order[j]] = j for every order[j] < n
 bool reorder_invert(const uint32_t* order, uint64_t n, uint32_t* inverse, hipStream_t stream);
 
+// Point-in-polygon ids and masks (crop.hip; the checks and the set's device memory are in crop_api.cpp, the index in polygon_index.hpp).  The
+// seams (pst_crop_kernel_shape):
+constexpr uint32_t kCropFlatPointsPerBlock = 1024;   // points one workgroup of the flat body serves from its LDS copy of the entries, four per lane
+constexpr uint32_t kCropBandedPointsPerBlock = 256;  // points per workgroup of the banded body, one lane each
+// Entries up to which the automatic choice takes the flat body.  Set by the LDS capacity -- 36 bytes per entry (the record and its polygon
+// index) make 36 KiB, four workgroups per compute unit of its 160 KiB -- because the measurement found no crossover below it: at 4, 64, 512
+// and 1024 entries on 10^8 points the flat body took 0.34 - 0.44 of the banded body's time (profiles/crop_1e8.json).
+constexpr uint32_t kCropFlatMaxEdges = 1024;
+constexpr uint32_t kCropNoPolygon = 0xFFFFFFFFu;
+// A set in device memory.  records: 4 doubles {lo.x, lo.y, hi.x, hi.y} each, 32-byte aligned; polygon: the polygon index of every record.
+// Flat: the n_records entries, sorted by polygon.  Banded: the band lists one after the other, list b = records offsets[b] .. offsets[b + 1],
+// each sorted by polygon; ymin, scale, bands: pst::polygon::Bands.
+struct CropSet {
+  const double* records;
+  const uint32_t* polygon;
+  const uint32_t* offsets;
+  uint32_t n_records, bands;
+  double xmin, ymin, xmax, ymax, scale;
+};
+// One launch.  ids (nullable): the smallest polygon index that contains point i, kCropNoPolygon without one.  mask (nullable): 1 iff
+// (id != kCropNoPolygon) != (outside != 0).  *count (nullable, zeroed by the caller) += the ones of the mask -- without a mask the ids that
+// name a polygon -- one integer atomic per wave.  flat needs n_records <= kCropFlatMaxEdges.
+bool crop_query(const Positions& pos, const CropSet& set, bool flat, uint32_t* ids, uint8_t* mask, int outside, unsigned long long* count, hipStream_t stream);
+// the byte at addr + i * stride = values[ids[i]] wherever ids[i] < n_values, i < n; *written (nullable, zeroed by the caller) += those points
+bool set_u8_from_ids(uint64_t addr, uint64_t stride, uint64_t n, const uint32_t* ids, const uint8_t* values, uint32_t n_values, unsigned long long* written,
+                     hipStream_t stream);
+
 }  // namespace pstk
