@@ -348,7 +348,9 @@ int pst_compute_normals_device(const pst_buffer* b, size_t k, double* d_normals,
  * the plan's, bit 1 / bit 2: more occupied boxes / more hand-backs than the plan provided for, bit 3: the exact search handed queries back
  * (far points: the coarser levels are host-driven), bit 4: degenerate neighbourhoods ([1] = how many: PST_ERR_NOT_ENOUGH_NEIGHBOURS of the
  * synchronous call) -- with any of bits 0-3 set the caller falls back to pst_compute_normals_into.  Clouds whose synchronous call did not
- * take the box search or left queries open (fewer than 2^20 points, far outliers) have no plan: PST_ERR_UNSUPPORTED. */
+ * take the box search or left queries open have no plan: PST_ERR_UNSUPPORTED with the reason in the message.  The box search is taken
+ * by clouds that fill their bounding box (from a few thousand points on: 10^5 points have a plan for every k from 3 to 64) and by
+ * larger clouds that do not but fit its directory budget; brute-force clouds, clouds with non-finite points or far outliers have none. */
 typedef struct pst_normals_plan pst_normals_plan;
 int pst_compute_normals_plan_create(const pst_buffer* b, size_t k, pst_buffer* dst, pst_normals_plan** out);
 int pst_normals_plan_destroy(pst_normals_plan* plan);

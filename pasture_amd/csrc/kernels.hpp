@@ -106,6 +106,11 @@ struct KnnPlan;
 KnnPlan* knn_plan_create(const KnnPlanRecord& rec, bool packed_source, hipStream_t stream);
 void knn_plan_free(KnnPlan* p);
 const KnnPlanRecord& knn_plan_record(const KnnPlan* p);
+// the capacities the plan sized from its record; the counters of its latest replay, copied to the host (synchronises the stream)
+struct KnnPlanCaps;
+struct KnnReplayCounters;
+KnnPlanCaps knn_plan_caps(const KnnPlan* p);
+bool knn_plan_read_counters(const KnnPlan* p, KnnReplayCounters& out, hipStream_t stream);
 // a plan made on a packed, 8-byte aligned Vec3f64 array searches its source in place and has no staging copy: it replays packed sources only;
 // a plan made on any other storage owns a staging copy and replays both
 bool knn_plan_accepts(const KnnPlan* p, const uint8_t* pos_base, uint64_t pos_stride);

@@ -1780,6 +1780,13 @@ bool knn_plan_accepts(const KnnPlan* p, const uint8_t* pos_base, uint64_t pos_st
   return (pos_stride == 24 && ((uintptr_t)pos_base & 7u) == 0) || p->xyz_own.p != nullptr;
 }
 const KnnPlanRecord& knn_plan_record(const KnnPlan* p) { return p->rec; }
+KnnPlanCaps knn_plan_caps(const KnnPlan* p) { return KnnPlanCaps{p->list_cap, p->fb_cap, p->all_boxes, p->xyz_own.p != nullptr}; }
+bool knn_plan_read_counters(const KnnPlan* p, KnnReplayCounters& out, hipStream_t stream) {
+  KnnCounters c;
+  if (!ok(hipMemcpyAsync(&c, p->counters.p, sizeof c, hipMemcpyDeviceToHost, stream)) || !ok(hipStreamSynchronize(stream))) return false;
+  out = KnnReplayCounters{c.n_finite, c.fb_count, c.box_count, {c.open_count[0], c.open_count[1]}, c.error_count};
+  return true;
+}
 
 bool run_normals_replay(KnnPlan* p, const uint8_t* pos_base, uint64_t pos_stride, double* out_normals_dev, double* out_curv_dev, uint32_t* out_knn_u32_dev,
                         uint64_t normal_attr, uint64_t normal_stride, uint64_t curv_attr, uint64_t curv_stride, unsigned long long* status2, hipStream_t stream) {

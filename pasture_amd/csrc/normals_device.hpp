@@ -177,6 +177,8 @@ __device__ __forceinline__ void cos_sin_third_angle(double s, double b, double& 
 //   * the matrix is nearly of rank one (collinear points): every cross product of two rows is a difference of nearly equal products, and the
 //     normal -- the largest of them -- carries a relative error of ~1e-16 / (lambda_1 / lambda_2); flagged when its norm in the scaled
 //     matrix is below 1e-4.
+//   * the determinant k0 is below the reference's threshold for its quadratic branch (|k0| < 2.2e-16, an ABSOLUTE test of a quantity that is
+//     pure rounding noise on exactly planar neighbourhoods): the reference's own covariance may lie on the other side of it.
 //   * two of the three cross products have norms within 1e-6 of each other: "the first maximum wins" (:395-426) is then decided by last bits,
 //     and on exactly planar neighbourhoods the candidates are parallel but may point in opposite directions (found by the round-5 structured
 //     volume test on a quantised plane: normal = -oracle's).
@@ -224,6 +226,10 @@ __device__ __forceinline__ Fit fit_from_covariance(double c00, double c01, doubl
     };
     if (__builtin_fabs(k0) < 2.220446049250313e-16) {
       quadratic();
+      // WHICH branch runs is decided by the last bits of the covariance where k0 is rounding noise (exactly planar neighbourhoods: every
+      // k = 3): with a covariance that is not the reference's own sequence of operations the reference may take the cubic, whose noise on
+      // nearly collinear points is a curvature of ~1e-12 against the 0 of this branch (100 000 uniform points, k = 3: 2 queries)
+      flagged = true;
     } else {
       const double one_third = 1.0 / 3.0;
       const double sqrt_3 = __builtin_sqrt(3.0);

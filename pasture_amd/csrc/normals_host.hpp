@@ -59,6 +59,9 @@ struct KnnPlanRecord {
   uint32_t n_list = 0, n_fb = 0; // what the recorded call saw: boxes listed, queries handed to the exact search
   const char* why_not = "";      // !valid: the reason
 };
+// What a plan sized from its record, and the device counters its latest replay left (read-only views for the tests of the replay)
+struct KnnPlanCaps { uint32_t list_cap = 0, fb_cap = 0, all_boxes = 0; bool staged = false; };  // staged: the plan owns a copy for sources that are no packed array
+struct KnnReplayCounters { unsigned long long n_finite = 0; uint32_t fb_count = 0, box_count = 0, open_count[2] = {0, 0}; int error_count = 0; };
 enum : uint32_t { KNN_STATUS_FINITE_COUNT = 1, KNN_STATUS_BOX_CAPACITY = 2, KNN_STATUS_FALLBACK_CAPACITY = 4, KNN_STATUS_OPEN_QUERIES = 8, KNN_STATUS_DEGENERATE = 16 };
 
 }  // namespace pstk
