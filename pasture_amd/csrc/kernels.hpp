@@ -53,6 +53,9 @@ constexpr int kResidentColumn = 4;        // columnar -> columnar conversion of 
 
 // K1/K2 fast path: columnar Vec3f64 stream. mode bits: 1 = affine, 2 = write dst, 4 = bounds.
 // partials must hold stream_partials_bytes(); out6 receives {min xyz, max xyz} when bounds are requested.
+// Modes 2 (plain copy) and 5 (bounds of the transformed values, nothing written) have no caller in the library; tests/test_stream_seams.py runs
+// them.  Mode 5 looks up the sign of a +-0 bound (zero_sign.hpp) in the UNTRANSFORMED source, the only values in memory: such a bound is zero by
+// value, its sign is not the index-order sign of the transformed values.
 int stream_grid();
 size_t stream_partials_bytes(uint64_t n_points, unsigned mode);  // bytes `partials` must hold for this launch
 void launch_vec3f64_stream(const double* src, double* dst, uint64_t n_points, const double scale[3], const double offset[3],

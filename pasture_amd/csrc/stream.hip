@@ -165,7 +165,8 @@ __global__ __launch_bounds__(kBlock) void vec3f64_stream_kernel(const StreamPara
     }
   }
 
-  // ragged doubles outside the 16-byte aligned vector body (at most one in front, two behind): block 0, lanes 0..2
+  // ragged doubles outside the 16-byte aligned vector body: block 0, lanes 0..2.  At most one in front (lane 0) and one behind (lane 1):
+  // n_doubles - vec_first - 2 * n_vec is 0 or 1, so lane 2 never finds a double of its own
   if (blockIdx.x == 0 && t < 3) {
     const uint64_t tail_first = p.vec_first + 2 * p.n_vec;
     uint64_t idx = ~0ull;

@@ -91,7 +91,7 @@ def test_bench_layout_conversion_vs_oracle(hip, oracle, pair):
     assert h.tobytes() == o.tobytes()
 
 
-@pytest.mark.parametrize("n", [0, 1, 2, 3, 767, 768, 769, 1535, 1536, 1537, 3073, 1_000_003])
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 511, 512, 513, 767, 768, 769, 1023, 1024, 1025, 1535, 1536, 1537, 3073, 8193, 1_000_003])
 @pytest.mark.parametrize("offset_points", [0, 1])
 def test_columnar_affine_convert_with_bounds_vs_oracle(hip, oracle, n, offset_points):
     """BASELINE.json configs[1] shape: columnar POSITION_3D -> columnar POSITION_3D with the LAS affine + AABB of the
