@@ -895,6 +895,62 @@ int pst_nn_kernel_shape(uint32_t* queries_per_block, uint32_t* reduce_block, uin
  * returns the calling thread's last call: ms = {query keys + sort, search}.  Zeros without the switch.  Host only. */
 int pst_nn_phase_times(double ms[2]);
 
+/* ---- M3C2 change detection ---------------------------------------------------------------------------------------------------------------
+ * What CloudCompare's M3C2 plugin and py4dgeo compute (Lague, Brodu & Leroux 2013; the reference has neither): for every CORE point the
+ * signed distance between two aligned clouds along the local normal, from the points of each cloud inside a cylinder around that normal,
+ * and a 95 % level of detection that says whether the distance is significant.  Where cloud-to-cloud distance is unsigned and grows with
+ * point spacing and roughness, this tells erosion from deposition and averages the roughness out.  The definitions; every arithmetic
+ * operation is a separately rounded f64 operation (no contraction), square roots and divisions correctly rounded:
+ *   inputs:       two indices, `reference` (cloud 1) and `compared` (cloud 2); n core points, the Position3D (Vec3f64) of any buffer (often a
+ *                 thinned cloud 1); the cylinder's radius R and half-length L = max_depth; min_points; registration_error.
+ *   normal:       of core point i.  d_normals given: row i of that array (DEVICE memory, f64 [n][3] in core order: what
+ *                 pst_compute_normals_device writes).  d_normals NULL: the normal `reference` holds for the reference point nearest to
+ *                 the core point, which is exactly the match of pst_nearest_neighbours_device with unbounded distance and no transform,
+ *                 ties as defined there; a `reference` without normals -> PST_ERR_MISSING_ATTRIBUTE.  Then
+ *                 nn = (nx*nx + ny*ny) + nz*nz, s = sqrt(nn), u = (nx/s, ny/s, nz/s).  With PST_M3C2_ORIENT_UP u is negated when uz < 0, or
+ *                 uz == 0 && uy < 0, or uz == 0 && uy == 0 && ux < 0.
+ *   invalid:      a core point that is not finite, that has no nearest point (d_normals NULL and no finite reference point), whose normal
+ *                 has a component that is not finite, or whose nn is 0 or not finite.  Its u is reported as three quiet NaNs
+ *                 (0x7FF8000000000000).
+ *   membership:   a finite point p of a cloud, d = p - c componentwise: t = (dx*ux + dy*uy) + dz*uz, w = (dx - t*ux, dy - t*uy, dz - t*uz),
+ *                 r2 = (wx*wx + wy*wy) + wz*wz; p is a member iff fabs(t) <= L && r2 <= R*R (R*R rounded once; both bounds inclusive).
+ *   per cloud X:  n_X = the number of members (u32), St_X = sum t, Stt_X = sum (t*t) over the members.  The order of summation is the
+ *                 implementation's, a fixed function of the inputs and the two grids (a fixed assignment of candidates to lanes and a
+ *                 fixed tree; no floating-point atomics): two calls give the same bits.  The COUNTS do not depend on the grids at all.
+ *   outputs:      for a valid core point with n_1 >= min_points && n_2 >= min_points, in this order of operations:
+ *                   mean_X = St_X / (double)n_X;  distance = mean_2 - mean_1
+ *                   q_X = Stt_X - (St_X*St_X) / (double)n_X;  var_X = (q_X > 0 ? q_X : 0) / (double)(n_X - 1)
+ *                   lod = 1.96 * (sqrt(var_1/(double)n_1 + var_2/(double)n_2) + registration_error)
+ *                   significant = fabs(distance) > lod
+ *                 With min_points == 1 and a count below 2, lod is NaN and significant 0 (the distance is still reported).  For any other
+ *                 core point, invalid ones included, distance and lod are NaN and significant is 0.  Counts and sums are always
+ *                 reported, 0 for an invalid core point; an index without a finite point gives counts 0.
+ * Checks, on the host before a device is looked for: null reference, compared or core; R and L finite and > 0; registration_error finite
+ * and >= 0; min_points >= 1; no unknown flag bits; at most 2^32 - 1 core points; at least one output pointer (n_significant counts as one);
+ * all PST_ERR_INVALID_ARGUMENT.  Then PST_ERR_MISSING_ATTRIBUTE when the core buffer's Position3D is not stored as Vec3f64, then when
+ * d_normals is NULL and `reference` has no normals; then the device (none: PST_ERR_NO_DEVICE, never a CPU path); then 2^32 - 16 core points
+ * and more -> PST_ERR_UNSUPPORTED.  Out of device memory is PST_ERR_OUT_OF_MEMORY and the next call works.  The core buffer may be
+ * interleaved or columnar, owned, sliced or external.
+ * Cost: one wave per core point walks the rows of cells its cylinder can touch in each grid; a core point whose cylinder misses a grid
+ * costs no search there.  A cylinder as long as a whole large grid tests every row of it. */
+#define PST_M3C2_ORIENT_UP 1u
+/* Synchronous.  Device outputs, each optional: d_distance, d_lod f64 [n]; d_significant u8 [n]; d_counts u32 [n][2] = {n_1, n_2};
+ * d_sums f64 [n][4] = {St_1, Stt_1, St_2, Stt_2}; d_unit_normals f64 [n][3] = the u used.  n_significant (host, optional): the number of
+ * significant core points.  At least one of the seven must be given. */
+int pst_m3c2_device(const pst_nn_index* reference, const pst_nn_index* compared, const pst_buffer* core, const double* d_normals, double radius, double max_depth,
+                    uint32_t min_points, double registration_error, uint32_t flags, double* d_distance, double* d_lod, uint8_t* d_significant, uint32_t* d_counts,
+                    double* d_sums, double* d_unit_normals, uint64_t* n_significant);
+/* The kernel's seams (each pointer optional; host only): core points one workgroup owns, lanes that share one core point (a whole wave:
+ * they search the rows of its cylinder in parallel and test the candidates across lanes). */
+int pst_m3c2_kernel_shape(uint32_t* cores_per_block, uint32_t* lanes_per_core);
+/* Measurement aid.  With PST_M3C2_TIMES=1 in the environment pst_m3c2_device brackets its three phases with stream events; this returns the
+ * calling thread's last call: ms = {normal lookup, core keys + sort, cylinder pass}.  Zeros without the switch.  Host only. */
+int pst_m3c2_phase_times(double ms[3]);
+/* Measurement aid.  With PST_M3C2_WORK=1 in the environment the cylinder pass counts its work (a second instantiation of the kernel: the
+ * counters cost nothing when the switch is off); this returns the calling thread's last call: out = {rows of cells searched, candidates
+ * tested, members}, over both clouds.  Zeros without the switch.  Host only. */
+int pst_m3c2_work(uint64_t out[3]);
+
 /* ---- Height above ground -----------------------------------------------------------------------------------------------------------------
  * What PDAL's filters.hag_nn and lidR's normalize_height(knnidw()) compute (the reference has neither): for every point of a QUERY cloud
  * the elevation of the ground under it, interpolated from its k nearest GROUND points IN THE XY PLANE with inverse squared distance

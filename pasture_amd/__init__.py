@@ -17,6 +17,7 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          dbscan_kernel_shape, dbscan_phase_times, extract_dbscan_clusters, RegionGrowingResult, extract_regions, region_growing,
                          region_growing_from_knn, region_kernel_shape, region_phase_times, NO_MATCH, NearestNeighbourIndex,
                          cloud_to_cloud_distances, distance_mask, icp, icp_plane, icp_plane_step, icp_step, nearest_neighbours, nearest_neighbours_device, nn_kernel_shape,
+                         M3C2Result, m3c2, m3c2_device, m3c2_kernel_shape, m3c2_phase_times, m3c2_work,
                          PmfParameters, classify_ground, extract_ground, grid_dilate, grid_erode, ground_mask, pmf_grid, pmf_kernel_shape, pmf_phase_times,
                          pmf_schedule, remove_ground, classification_mask, hag_kernel_shape, hag_phase_times, height_above_ground,
                          height_above_ground_device, normalize_height, Raster, grid_fill, raster_kernel_shape, raster_phase_times, rasterize,

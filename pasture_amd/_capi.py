@@ -220,6 +220,10 @@ _PRODUCT_SIGNATURES = {
     "icp_plane": [_P, _P, _D3, C.c_double, C.c_uint32, C.c_double, _D3, _D3, _U64P, _U32P],
     "nn_kernel_shape": [_U32P, _U32P, _U32P],
     "nn_phase_times": [_D3],
+    "m3c2_device": [_P, _P, _P, _P, C.c_double, C.c_double, C.c_uint32, C.c_double, C.c_uint32, _P, _P, _P, _P, _P, _P, _U64P],
+    "m3c2_kernel_shape": [_U32P, _U32P],
+    "m3c2_phase_times": [_D3],
+    "m3c2_work": [_U64P],
     "height_above_ground_device": [_P, _P, _P, C.c_uint32, C.c_double, C.c_double, _P, _P, _U64P, _U64P, _D3, _U32P],
     "buffer_u8_equals_mask_device": [_P, C.c_char_p, C.c_uint8, _P],
     "hag_kernel_shape": [_U32P, _U32P, _U32P],

@@ -1025,6 +1025,100 @@ def nn_phase_times(api=None):
     return _phase_times(api, "nn_phase_times", 2)
 
 
+# ---- M3C2 change detection: signed distances along normals (include/pasture_amd.h) --------------------------------------------------------------
+
+M3C2_ORIENT_UP = 1
+
+
+@dataclass
+class M3C2Result:
+    """Per core point: the signed distance from the reference to the compared cloud along the normal, its 95 % level of detection, whether
+    |distance| exceeds it, the members of the two cylinders (n, 2) and their spreads sqrt(var_X) (n, 2); n_significant = significant.sum().
+    NaN where a figure is not defined (too few members, an invalid core point).  sums (n, 4) = St_1, Stt_1, St_2, Stt_2 and unit_normals
+    (n, 3) with return_sums."""
+    distance: np.ndarray
+    lod: np.ndarray
+    significant: np.ndarray
+    counts: np.ndarray
+    spread: np.ndarray
+    n_significant: int
+    sums: Optional[np.ndarray] = None
+    unit_normals: Optional[np.ndarray] = None
+
+
+def m3c2_device(core: _Buffer, reference: NearestNeighbourIndex, compared: NearestNeighbourIndex, radius: float, max_depth: float, normals_ptr: int = 0,
+                min_points: int = 4, registration_error: float = 0.0, orient_up: bool = False, distance_ptr: int = 0, lod_ptr: int = 0, significant_ptr: int = 0,
+                counts_ptr: int = 0, sums_ptr: int = 0, unit_normals_ptr: int = 0, count_significant: bool = True) -> Optional[int]:
+    """M3C2 of the core points against two indexed clouds, results in caller-owned DEVICE memory (addresses; 0 = not wanted): distance and lod
+    f64 [n], significant u8 [n], counts u32 [n][2], sums f64 [n][4], unit normals f64 [n][3].  normals_ptr: f64 [n][3] in core order on the
+    device, or 0 for the normal `reference` holds for the nearest reference point.  Nothing is copied; returns the number of significant core
+    points (None with count_significant=False)."""
+    nsig = C.c_uint64()
+    core.api.m3c2_device(reference._h, compared._h, core._h, C.c_void_p(normals_ptr or None), radius, max_depth, min_points, registration_error,
+                         M3C2_ORIENT_UP if orient_up else 0, C.c_void_p(distance_ptr or None), C.c_void_p(lod_ptr or None), C.c_void_p(significant_ptr or None),
+                         C.c_void_p(counts_ptr or None), C.c_void_p(sums_ptr or None), C.c_void_p(unit_normals_ptr or None), C.byref(nsig) if count_significant else None)
+    return nsig.value if count_significant else None
+
+
+class _NormalIndexFor(_IndexFor):
+    """_IndexFor whose own index carries the normals compute_normals_device estimates (NearestNeighbourIndex.with_normals)"""
+
+    def __init__(self, target_or_index, k_nn: int):
+        self.own = not isinstance(target_or_index, NearestNeighbourIndex)
+        self.index = NearestNeighbourIndex.with_normals(target_or_index, k_nn) if self.own else target_or_index
+
+
+def m3c2(core: _Buffer, reference, compared, radius: float, max_depth: float, normals=None, min_points: int = 4, registration_error: float = 0.0,
+         orient_up: bool = False, return_sums: bool = False, k_nn: int = 16) -> M3C2Result:
+    """M3C2 (Lague, Brodu & Leroux 2013; CloudCompare's plugin, py4dgeo): per core point the signed distance between two aligned clouds along the
+    local normal, from the points of each cloud inside a cylinder of `radius` reaching `max_depth` to either side, with the 95 % level of
+    detection 1.96 * (sqrt(var_1/n_1 + var_2/n_2) + registration_error).  `reference` and `compared` are buffers or NearestNeighbourIndex
+    objects; `normals` is the address of f64 [n][3] on the device, a host array (n, 3), or None: the normal of the nearest reference point,
+    for which a `reference` given as a buffer is indexed with NearestNeighbourIndex.with_normals(reference, k_nn)."""
+    from .layout import PointAttributeDataType as T
+    api, n = core.api, core.len()
+    nptr, keep = _device_input(api, normals, T.F64, np.float64, 3 * n, "normals")
+    dist, lod, sig = _DeviceArray(api, T.F64, n), _DeviceArray(api, T.F64, n), _DeviceArray(api, T.U8, n)
+    counts, sums = _DeviceArray(api, T.U32, 2 * n), _DeviceArray(api, T.F64, 4 * n)
+    unit = _DeviceArray(api, T.F64, 3 * n) if return_sums else None
+    with (_NormalIndexFor(reference, k_nn) if normals is None else _IndexFor(reference)) as ref, _IndexFor(compared) as cmp:
+        nsig = m3c2_device(core, ref, cmp, radius, max_depth, nptr, min_points, registration_error, orient_up, dist.ptr or 1, lod.ptr or 1, sig.ptr or 1,
+                           counts.ptr or 1, sums.ptr or 1, unit.ptr or 1 if unit else 0)
+    del keep
+    c = counts.to_numpy().reshape(n, 2)
+    s = sums.to_numpy().reshape(n, 4)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = c.astype(np.float64)
+        q = s[:, 1::2] - (s[:, 0::2] * s[:, 0::2]) / m
+        spread = np.sqrt(np.where(q > 0.0, q, 0.0) / (c.astype(np.int64) - 1))
+    spread[c < 2] = np.nan
+    return M3C2Result(dist.to_numpy(), lod.to_numpy(), sig.to_numpy().astype(bool), c, spread, nsig, s if return_sums else None,
+                      unit.to_numpy().reshape(n, 3) if unit else None)
+
+
+def m3c2_kernel_shape(api=None) -> dict:
+    """The seams of the M3C2 kernel: core points one workgroup owns, lanes that share one core point."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(2)]
+    (api or product_api()).m3c2_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("cores_per_block", "lanes_per_core"), (x.value for x in v)))
+
+
+def m3c2_phase_times(api=None):
+    """(normal lookup, core keys + sort, cylinder pass) in milliseconds of this thread's last m3c2* call; zeros unless PST_M3C2_TIMES=1 was set
+    when the library first ran one."""
+    return _phase_times(api, "m3c2_phase_times", 3)
+
+
+def m3c2_work(api=None) -> dict:
+    """rows of cells searched, candidates tested and members found by this thread's last m3c2* call, over both clouds; zeros unless
+    PST_M3C2_WORK=1 was set when the library first ran one."""
+    from ._capi import product_api
+    out = (C.c_uint64 * 3)()
+    (api or product_api()).m3c2_work(out)
+    return dict(zip(("rows", "candidates", "members"), (int(x) for x in out)))
+
+
 # ---- height above ground from the k nearest ground points in the XY plane (include/pasture_amd.h) ---------------------------------------------
 
 def classification_mask(buffer: _Buffer, value: int, device_mask_ptr: int) -> None:

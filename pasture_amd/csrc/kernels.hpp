@@ -325,6 +325,27 @@ size_t nn_plane_partials_bytes(uint64_t n);
 bool nn_plane_sums(const Positions& pos, const NnTransform& t, const uint32_t* at, const double* xs, const double* ys, const double* zs, const double* nx,
                    const double* ny, const double* nz, const double origin[3], void* partials, NnPlaneSums* rec, hipStream_t stream);
 
+// M3C2 change detection (m3c2.hip; the argument checks, the scratch and the order of the launches are in m3c2_api.cpp).  The seams
+// (pst_m3c2_kernel_shape):
+constexpr uint32_t kM3c2LanesPerCore = 64;   // lanes that share one core point: ONE wave searches the rows of its cylinder and tests the candidates
+constexpr uint32_t kM3c2CoresPerBlock = 4;   // core points one workgroup of 256 threads owns, one per wave
+// one indexed cloud as the cylinder walk reads it (the arrays of a pst_nn_index; nf == 0: nothing is read)
+struct M3c2Cloud { const unsigned long long* keys; const double *xs, *ys, *zs; uint32_t nf; NnGrid g; };
+struct M3c2Args {
+  const uint8_t* core_base; uint64_t core_stride; uint32_t n;
+  const uint32_t* order;                // core point of sorted position s (null: s itself)
+  const double* normals;                // f64 [n][3] in core order, or null: nx / ny / nz [at[i]]
+  const uint32_t* at;                   // per core point the position of its nearest reference point in the index's sorted arrays (0xFFFFFFFF: none)
+  const double *nx, *ny, *nz;
+  M3c2Cloud cloud[2];                   // reference, compared
+  double radius, max_depth, radius2, registration_error;
+  uint32_t min_points, flags;
+  double* distance; double* lod; uint8_t* significant; uint32_t* counts; double* sums; double* unit_normals;  // each optional
+  unsigned long long* n_significant;    // one counter, zeroed by the launcher
+  unsigned long long* work;             // three counters (rows searched, candidates tested, members), zeroed by the launcher; null: not counted
+};
+bool m3c2_run(const M3c2Args& a, hipStream_t stream);
+
 // Height above ground from the k nearest ground points in the XY plane (hag.hip; the grid is sized in hag_grid.hpp, the scratch and the order
 // of the launches are in hag_api.cpp).  The seams (pst_hag_kernel_shape):
 constexpr uint32_t kHagQueriesPerBlock = 64;       // queries one workgroup of the search kernel owns: ONE wave, one lane per query
