@@ -1006,6 +1006,70 @@ int pst_hag_kernel_shape(uint32_t* queries_per_block, uint32_t* max_k, uint32_t*
  * switch.  Host only. */
 int pst_hag_phase_times(double ms[3]);
 
+/* ---- Individual trees: tops by a local-maximum filter, crowns after Silva et al. 2016 -----------------------------------------------------
+ * What lidR's locate_trees(lmf(ws, hmin)) and segment_trees(silva2016()) and PDAL's filters.litree are for (the reference has neither):
+ * which points are tree tops, and which tree every point belongs to.  Every arithmetic operation below is a separately rounded f64
+ * operation (no contraction); no square root appears anywhere.  The definitions:
+ *   height:       h_i = the z of point i's Position3D (Vec3f64), or d_heights[i] when that column is given: DEVICE memory, len x f64 -- how
+ *                 the d_hag of pst_height_above_ground_device is fed in.  x and y come from the position; z is not consulted when
+ *                 d_heights is given.
+ *   valid:        x, y and h are finite and d_mask is NULL or d_mask[i] != 0 (DEVICE memory, len bytes).
+ *   candidates:   C = the valid points with h_i >= min_height (finite).
+ *   window:       window = {a, b, r_min, r_max}, RADII: r_i = min(max(a + b*h_i, r_min), r_max); a, b finite, 0 <= r_min <= r_max, r_min
+ *                 finite, r_max may be +inf.  (lidR's ws is a diameter.)  A fixed window is b = 0.  j is in i's window iff
+ *                 dx*dx + dy*dy <= r_i*r_i, inclusive, dx = x_j - x_i, dy = y_j - y_i.
+ *   dominates:    j dominates i iff h_j > h_i, or h_j == h_i and j < i in buffer order (-0.0 == +0.0).
+ *   tops:         candidate i is a tree top iff no OTHER candidate in i's window dominates it.  The window is i's own: with b != 0 the
+ *                 relation is deliberately asymmetric, as in lidR.  Points below min_height dominate nobody.  With r_i == 0 the window
+ *                 still holds the exact duplicates of i in x and y.
+ *   numbering:    the trees are the tops numbered 0 .. n_trees - 1 by descending height, ties (-0.0 and +0.0 tie) by ascending buffer
+ *                 index: tallest first, so that pst_cluster_mask_device(first, count) selects the tallest trees.
+ *   crowns:       parameters max_crown_factor >= 0 (finite; the crown DIAMETER as a share of the tree's height), exclusion in [0, 1],
+ *                 min_height.  The trees T are the VALID points with a non-zero byte in d_top_mask, whatever their height (a caller may
+ *                 edit the mask), numbered as above, H_t their heights.  For every valid point p with h_p >= min_height: t = the tree of
+ *                 lexicographically smallest (d2, buffer index of the top), d2 as above from p to the top; rc = (0.5*max_crown_factor) * H_t;
+ *                 tree_id[p] = the number of t iff d2 <= rc*rc && h_p >= exclusion*H_t, else 0xFFFFFFFF.  The NEAREST top is chosen
+ *                 first and then tested, as lidR does -- not the nearest among those that pass.  Every other point gets 0xFFFFFFFF.
+ *                 counts[t] = the points labelled t, n_labelled their sum.
+ * Both results are functions of the cloud, the heights, the masks and the parameters alone: not of the grid, not of the storage kind; two
+ * calls write the same bytes.
+ * Checks: null arguments and invalid parameters (min_height not finite; the window's conditions above; max_crown_factor; exclusion; a
+ * negative, NaN or infinite cell_edge) are answered before a device is looked for; then PST_ERR_MISSING_ATTRIBUTE when Position3D is not
+ * stored as Vec3f64; an empty buffer is then PST_OK on the host with nothing written and zeros in the counts and the grid; then the device
+ * (none: PST_ERR_NO_DEVICE, never a CPU path); then 2^32 - 16 points and more -> PST_ERR_UNSUPPORTED.  Out of device memory is
+ * PST_ERR_OUT_OF_MEMORY and the next call works.
+ * Synchronous.  d_top_mask: DEVICE memory, len bytes, 1 for a top and 0 for every other point: what pst_buffer_filter_into and
+ * pst_segment_trees_device take.  d_top_indices (DEVICE, u32, optional): the buffer indices of the tops IN TREE-NUMBER ORDER when they fit
+ * `capacity`; more tops than that -> PST_ERR_RANGE with the mask written and the counts set (the pst_plane_inliers convention).
+ * n_candidates = |C|, n_tops, grid_min_and_edge = {min x, min y, final cell edge} and grid_dim = {columns, rows} of the candidate grid that
+ * was used: each optional, host.  No candidate: an all-zero mask, zero counts, a zero grid.  cell_edge > 0: the grid's cell edge; 0:
+ * automatic (half the radius of a window at half the largest |h|, not below a sparse-cloud floor).  Either is doubled until no axis has
+ * more than 2^21 - 1 cells and the grid no more than 2^26.
+ * Cost: a candidate first tests the candidates of the 3 x 3 cells around it, which decides nearly every point of a canopy; the others, the
+ * tops among them, get one wave each for the rest of their window. */
+int pst_tree_tops_device(const pst_buffer* b, const double* d_heights, const uint8_t* d_mask, double min_height, const double window[4], double cell_edge,
+                         uint8_t* d_top_mask, uint32_t* d_top_indices, size_t capacity, uint64_t* n_candidates, uint64_t* n_tops, double grid_min_and_edge[3],
+                         uint32_t grid_dim[2]);
+/* Synchronous.  d_tree_id: DEVICE memory, len x u32, the labels (what pst_cluster_mask_device and pst_buffer_set_u8_from_ids_device take).
+ * d_tree_counts (DEVICE, u32, optional): counts[t] when the trees fit counts_capacity; more trees than that -> PST_ERR_RANGE with the
+ * labels written and *n_trees, *n_labelled set.  No tree: every label 0xFFFFFFFF.  The search is bounded by
+ * rc_max = (0.5*max_crown_factor) * max |H|: a top farther away fails its own test.  cell_edge: of the grid over the tops, as above. */
+int pst_segment_trees_device(const pst_buffer* b, const double* d_heights, const uint8_t* d_mask, const uint8_t* d_top_mask, double min_height, double max_crown_factor,
+                             double exclusion, double cell_edge, uint32_t* d_tree_id, uint32_t* d_tree_counts, size_t counts_capacity, uint64_t* n_trees,
+                             uint64_t* n_labelled);
+/* The kernels' seams (each pointer optional; host only): candidates one workgroup of the near pass owns (one lane each), survivors one
+ * workgroup of the far pass owns (one wave each), queries one workgroup of the crown search owns, points per block partial of the member
+ * pass. */
+int pst_trees_kernel_shape(uint32_t* points_per_block, uint32_t* survivors_per_block, uint32_t* queries_per_block, uint32_t* bounds_points_per_block);
+/* Measurement aid.  With PST_TREES_TIMES=1 in the environment both calls bracket their phases with stream events; this returns the calling
+ * thread's last call: ms = {candidate index, local-maximum filter, numbering, top index + crown search}; pst_tree_tops_device leaves the
+ * last one 0, pst_segment_trees_device the first two.  Zeros without the switch.  Host only. */
+int pst_trees_phase_times(double ms[4]);
+/* Measurement aid: out = {candidates, candidates the near pass left undecided, candidates the far pass tested} of the calling thread's last
+ * pst_tree_tops_device; the last one is counted only with PST_TREES_WORK=1 in the environment (a second instantiation of the kernel), else
+ * 0.  Host only. */
+int pst_trees_work(uint64_t out[3]);
+
 /* ---- Rasterisation: per-cell statistics of a cloud on an XY grid -------------------------------------------------------------------------
  * What PDAL's writers.gdal computes before it writes a file (the reference has nothing like it): a surface model (MAX of z), a canopy height
  * model (MAX of the height above ground), a density image (COUNT), an intensity image (MEAN), and the hole filler every such raster

@@ -262,6 +262,11 @@ _PRODUCT_SIGNATURES = {
     "polygon_mask_device": [_P, _P, C.c_int, _P, _U64P],
     "buffer_set_u8_from_ids_device": [_P, C.c_char_p, _P, _P, C.c_uint32, _U64P],
     "crop_kernel_shape": [_U32P, _U32P, _U32P],
+    "tree_tops_device": [_P, _P, _P, C.c_double, _D3, C.c_double, _P, _P, _SZ, _U64P, _U64P, _D3, _U32P],
+    "segment_trees_device": [_P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _SZ, _U64P, _U64P],
+    "trees_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
+    "trees_phase_times": [_D3],
+    "trees_work": [_U64P],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -1686,3 +1686,165 @@ def crop_kernel_shape(api=None) -> dict:
     v = [C.c_uint32() for _ in range(3)]
     (api or product_api()).crop_kernel_shape(*[C.byref(x) for x in v])
     return dict(zip(("flat_points_per_block", "banded_points_per_block", "flat_max_edges"), (x.value for x in v)))
+
+
+# ---- individual trees: tops by a local-maximum filter, crowns after Silva et al. 2016 (include/pasture_amd.h) ----------------------------------
+
+NO_TREE = 0xFFFFFFFF
+
+
+@dataclass(frozen=True)
+class TreeTops:
+    """What tree_tops returns: `indices` (uint32) = the buffer indices of the tops in tree-number order -- by descending height, ties by
+    ascending index --, `heights` (float64) their heights, `n_candidates` the valid points at or above min_height, `n_tops` = len(indices);
+    `mask` (uint8, one byte per point) is 1 at the tops."""
+    indices: np.ndarray
+    heights: np.ndarray
+    n_candidates: int
+    n_tops: int
+    mask: np.ndarray
+
+
+@dataclass(frozen=True)
+class TreeSegmentation:
+    """What segment_trees returns: `tree_id` (uint32 per point, NO_TREE = 0xFFFFFFFF without a tree; None when the labels went to device
+    memory), `counts` (uint32, counts[t] = points labelled t), `n_trees`, `n_labelled` = counts.sum()."""
+    tree_id: Optional[np.ndarray]
+    counts: np.ndarray
+    n_trees: int
+    n_labelled: int
+
+
+def _window_radii(window):
+    """window in DIAMETERS, as lidR's ws: a number (fixed), or (a, b, min, max) for a + b*h clamped -> the four radii of the C ABI"""
+    if isinstance(window, (int, float, np.integer, np.floating)):
+        r = 0.5 * float(window)
+        return (r, 0.0, r, r)
+    a, b, lo, hi = (float(v) for v in window)
+    return (0.5 * a, 0.5 * b, 0.5 * lo, 0.5 * hi)
+
+
+def tree_tops_device(buffer: _Buffer, window_radii, min_height: float, device_top_mask_ptr: int, device_heights_ptr: int = 0, device_mask_ptr: int = 0,
+                     cell_edge: float = 0.0, device_top_indices_ptr: int = 0, capacity: int = 0) -> dict:
+    """pst_tree_tops_device: lidR's locate_trees(lmf()) on the device.  window_radii = (a, b, r_min, r_max), RADII: r = min(max(a + b*h,
+    r_min), r_max).  A valid point (x, y, h finite, mask byte not zero) with h >= min_height is a top iff no other such point within r of
+    it in the XY plane is higher (equal heights: has the lower index).  h = z, or the float64 DEVICE column at device_heights_ptr.  Writes
+    len(buffer) bytes at device_top_mask_ptr and, with device_top_indices_ptr and enough capacity, the tops' indices (uint32) in tree order:
+    tallest first.  Returns {"n_candidates", "n_tops", "origin", "cell_edge", "dim"}; the last three describe the grid that was used, which
+    the result does not depend on."""
+    nc, nt, me, dim = C.c_uint64(), C.c_uint64(), (C.c_double * 3)(), (C.c_uint32 * 2)()
+    w = (C.c_double * 4)(*[float(v) for v in window_radii])
+    buffer.api.tree_tops_device(buffer._h, C.c_void_p(int(device_heights_ptr) or None), C.c_void_p(int(device_mask_ptr) or None), min_height, w, cell_edge,
+                                C.c_void_p(int(device_top_mask_ptr) or None), C.c_void_p(int(device_top_indices_ptr) or None), capacity, C.byref(nc), C.byref(nt), me, dim)
+    return {"n_candidates": nc.value, "n_tops": nt.value, "origin": (me[0], me[1]), "cell_edge": me[2], "dim": (dim[0], dim[1])}
+
+
+def tree_tops(buffer: _Buffer, window=(3.0, 0.0, 3.0, 3.0), min_height: float = 2.0, heights=None, mask=None, cell_edge: float = 0.0) -> TreeTops:
+    """lidR's locate_trees(lmf(ws = window, hmin = min_height)).  `window` is a DIAMETER, as lidR's ws (window = 2*r): a number for a fixed
+    window, or (a, b, min, max) for a + b*h clamped to [min, max].  heights: None for z, a numpy float64 array (uploaded) or the address of a
+    float64 DEVICE column -- the heights above ground, as a rule.  mask: None, a numpy uint8 array or a DEVICE address."""
+    from .layout import PointAttributeDataType as T
+    api, n = buffer.api, buffer.len()
+    hptr, hheld = _device_input(api, heights, T.F64, np.float64, n, "heights")
+    mptr, mheld = _device_input(api, mask, T.U8, np.uint8, n, "mask")
+    top = _DeviceArray(api, T.U8, n)
+    radii = _window_radii(window)
+    info = tree_tops_device(buffer, radii, min_height, top.ptr or 1, hptr, mptr, cell_edge)
+    nt = info["n_tops"]
+    idx = _DeviceArray(api, T.U32, nt)
+    if nt:
+        tree_tops_device(buffer, radii, min_height, top.ptr, hptr, mptr, cell_edge, idx.ptr, nt)
+    indices = idx.to_numpy().astype(np.uint32) if nt else np.zeros(0, dtype=np.uint32)
+    if heights is None:
+        from .layout import attributes as A
+        hs = buffer.view_attribute(A.POSITION_3D)[indices.astype(np.int64), 2] if nt else np.zeros(0)
+    elif hheld is not None:
+        hs = hheld.to_numpy()[indices.astype(np.int64)]
+    else:  # a caller's device column: gathered through a one-attribute buffer over it
+        hs = _read_device_f64(api, hptr, n)[indices.astype(np.int64)] if nt else np.zeros(0)
+    del mheld
+    return TreeTops(indices, np.asarray(hs, dtype=np.float64), info["n_candidates"], nt, top.to_numpy().astype(np.uint8) if n else np.zeros(0, dtype=np.uint8))
+
+
+def _read_device_f64(api, ptr: int, count: int) -> np.ndarray:
+    """`count` float64 values at a caller's DEVICE address, copied to the host"""
+    from .buffers import ExternalColumnsBuffer
+    from .layout import PointAttributeDataType as T, PointLayout
+    attribute = PointAttributeDefinition.custom("Values", T.F64)
+    view = ExternalColumnsBuffer([ptr], PointLayout.from_attributes([attribute], api=api), count)
+    return view.view_attribute(attribute)
+
+
+def segment_trees_device(buffer: _Buffer, device_top_mask_ptr: int, device_tree_id_ptr: int, max_crown_factor: float = 0.6, exclusion: float = 0.3,
+                         min_height: float = 2.0, device_heights_ptr: int = 0, device_mask_ptr: int = 0, cell_edge: float = 0.0, device_counts_ptr: int = 0,
+                         counts_capacity: int = 0) -> dict:
+    """pst_segment_trees_device: lidR's segment_trees(silva2016()) on the device.  The trees are the valid points with a non-zero byte in the
+    DEVICE mask at device_top_mask_ptr, numbered by descending height (ties: ascending index).  A valid point with h >= min_height looks up
+    its NEAREST top in the XY plane (ties: the top of smaller index) and gets that tree's number iff it lies within
+    0.5 * max_crown_factor * H of it and h >= exclusion * H, H the top's height; every other point gets NO_TREE.  Writes len(buffer) uint32
+    at device_tree_id_ptr and, with device_counts_ptr and enough capacity, the points per tree (uint32).  Returns {"n_trees", "n_labelled"}."""
+    nt, nl = C.c_uint64(), C.c_uint64()
+    buffer.api.segment_trees_device(buffer._h, C.c_void_p(int(device_heights_ptr) or None), C.c_void_p(int(device_mask_ptr) or None),
+                                    C.c_void_p(int(device_top_mask_ptr) or None), min_height, max_crown_factor, exclusion, cell_edge,
+                                    C.c_void_p(int(device_tree_id_ptr) or None), C.c_void_p(int(device_counts_ptr) or None), counts_capacity, C.byref(nt), C.byref(nl))
+    return {"n_trees": nt.value, "n_labelled": nl.value}
+
+
+def segment_trees(buffer: _Buffer, tops, max_crown_factor: float = 0.6, exclusion: float = 0.3, min_height: float = 2.0, heights=None, mask=None,
+                  cell_edge: float = 0.0, device_tree_id_ptr: Optional[int] = None) -> TreeSegmentation:
+    """lidR's segment_trees(silva2016(max_cr_factor, exclusion)): see segment_trees_device.  tops: a TreeTops, a numpy uint8 mask with one
+    byte per point, or the address of such bytes in DEVICE memory.  heights, mask: as tree_tops.  With device_tree_id_ptr the labels stay in
+    DEVICE memory there and the result's tree_id is None."""
+    from .layout import PointAttributeDataType as T
+    api, n = buffer.api, buffer.len()
+    hptr, hheld = _device_input(api, heights, T.F64, np.float64, n, "heights")
+    mptr, mheld = _device_input(api, mask, T.U8, np.uint8, n, "mask")
+    tptr, theld = _device_input(api, tops.mask if isinstance(tops, TreeTops) else tops, T.U8, np.uint8, n, "tops")
+    ids = _DeviceArray(api, T.U32, n) if device_tree_id_ptr is None else None
+    id_ptr = (ids.ptr or 1) if ids is not None else int(device_tree_id_ptr)
+    info = segment_trees_device(buffer, tptr or 1, id_ptr, max_crown_factor, exclusion, min_height, hptr, mptr, cell_edge)
+    nt = info["n_trees"]
+    counts = _DeviceArray(api, T.U32, nt)
+    if nt:
+        info = segment_trees_device(buffer, tptr, id_ptr, max_crown_factor, exclusion, min_height, hptr, mptr, cell_edge, counts.ptr, nt)
+    del hheld, mheld, theld
+    tree_id = None if ids is None else (ids.to_numpy().astype(np.uint32) if n else np.zeros(0, dtype=np.uint32))
+    return TreeSegmentation(tree_id, counts.to_numpy().astype(np.uint32) if nt else np.zeros(0, dtype=np.uint32), nt, info["n_labelled"])
+
+
+def extract_tree(buffer: _Buffer, segmentation_or_ptr, first: int = 0, count: int = 1, out_buffer_type=None):
+    """The points of trees first .. first + count - 1 (tree 0 is the tallest) in buffer order with all their attributes: a TreeSegmentation
+    (its labels are uploaded) or the address of len(buffer) uint32 labels in DEVICE memory, through cluster_mask and filter.  `buffer` is
+    columnar (filter is defined on HashMapBuffer)."""
+    from .layout import PointAttributeDataType as T
+    labels = segmentation_or_ptr.tree_id if isinstance(segmentation_or_ptr, TreeSegmentation) else segmentation_or_ptr
+    if labels is None:
+        raise ValueError("this TreeSegmentation left its labels in device memory: pass their address")
+    ptr, held = _device_input(buffer.api, labels, T.U32, np.uint32, buffer.len(), "tree ids")
+    out = _filter_by_device_mask(buffer, out_buffer_type, lambda p: cluster_mask(ptr, buffer.len(), first, count, p, api=buffer.api))[0]
+    del held
+    return out
+
+
+def trees_kernel_shape(api=None) -> dict:
+    """The seams of the tree kernels: candidates per workgroup of the near pass of the filter (one lane each), survivors per workgroup of its
+    far pass (one wave each), queries per workgroup of the crown search, points per block partial of the member pass."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(4)]
+    (api or product_api()).trees_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "survivors_per_block", "queries_per_block", "bounds_points_per_block"), (x.value for x in v)))
+
+
+def trees_phase_times(api=None):
+    """(candidate index, local-maximum filter, numbering, top index + crown search) in milliseconds of this thread's last tree_tops* or
+    segment_trees* call; zeros unless PST_TREES_TIMES=1 was set when the library first ran one."""
+    return _phase_times(api, "trees_phase_times", 4)
+
+
+def trees_work(api=None) -> dict:
+    """Of this thread's last tree_tops* call: the candidates, those the near pass left to the far pass, and the candidates the far pass
+    tested (counted only with PST_TREES_WORK=1 in the environment, else 0)."""
+    from ._capi import product_api
+    out = (C.c_uint64 * 3)()
+    (api or product_api()).trees_work(out)
+    return dict(zip(("candidates", "survivors", "far_tested"), (int(x) for x in out)))

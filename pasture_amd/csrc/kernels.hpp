@@ -8,6 +8,7 @@
 #include "../../include/pasture_amd.h"
 #include "cluster_grid.hpp"
 #include "hag_grid.hpp"
+#include "trees_window.hpp"
 #include "plan.h"
 
 namespace pstk {
@@ -541,5 +542,47 @@ bool crop_query(const Positions& pos, const CropSet& set, bool flat, uint32_t* i
 // the byte at addr + i * stride = values[ids[i]] wherever ids[i] < n_values, i < n; *written (nullable, zeroed by the caller) += those points
 bool set_u8_from_ids(uint64_t addr, uint64_t stride, uint64_t n, const uint32_t* ids, const uint8_t* values, uint32_t n_values, unsigned long long* written,
                      hipStream_t stream);
+
+// Individual trees: the local-maximum filter and the crowns (trees.hip; the window in trees_window.hpp; the checks, the scratch and the order
+// of the launches in trees_api.cpp).  The index is hag.hip's -- the same keys, sort, dense directory and suffix minimum -- over the members a
+// byte selects, with the height of every member next to its x and y.  The seams (pst_trees_kernel_shape):
+constexpr uint32_t kTreesPointsPerBlock = 256;         // candidates one workgroup of the near pass owns, one lane each
+constexpr uint32_t kTreesSurvivorsPerBlock = 4;        // survivors one workgroup of the far pass owns, ONE wave each
+constexpr uint32_t kTreesQueriesPerBlock = 64;         // queries one workgroup of the crown search owns: one wave, one lane per query
+constexpr uint32_t kTreesBoundsPointsPerBlock = 4096;  // points per block partial of the member pass, sixteen per lane
+// what a point's height is and which points take part: heights == nullptr: z; mask == nullptr: every point
+struct TreesInput { Positions pos; const double* heights; const uint8_t* mask; };
+// the device-side record of the member pass: the AABB of the members in x and y, the largest |h| among them, their number
+struct TreesBounds { double min_x, min_y, max_x, max_y, max_abs_h; unsigned long long count; };
+size_t trees_bounds_partials_bytes(uint64_t n);
+// member[i] = 1 iff x, y and h of point i are finite, both masks (in.mask, also; each nullable) are not zero there and h >= floor (-inf:
+// every valid point), else 0; block partials of the members' bounds, then one workgroup folds them into *rec; no atomics
+bool trees_members(const TreesInput& in, const uint8_t* also, double floor, uint8_t* member, void* partials, TreesBounds* rec, hipStream_t stream);
+// keys[e] = (cy << bits[0]) | cx of point i = subset ? subset[e] : e, with bit bits[0] + bits[1] set when member (nullable) is 0 there; e < count
+bool trees_keys(const Positions& pos, const uint32_t* subset, const uint8_t* member, uint64_t count, const HagGrid& g, uint32_t* keys, hipStream_t stream);
+// x, y, h and the buffer index (index, nullable) of point i = subset ? subset[order[s]] : order[s] for the m sorted positions s
+bool trees_gather(const TreesInput& in, const uint32_t* subset, const uint32_t* order, uint32_t m, double* xs, double* ys, double* hs, uint32_t* index, hipStream_t stream);
+// The near pass over the nc sorted candidates: the 3 x 3 cells around a candidate, clipped to its window's box.  A dominator there decides
+// it (no top); none and a box inside those cells decides it too (top_mask[index[s]] = 1); flags[s] = 1 for the others, flags[nc] = 0.
+bool trees_filter_near(const TreeWindow& w, const HagGrid& g, const uint32_t* dir, const double* xs, const double* ys, const double* hs, const uint32_t* index, uint32_t nc,
+                       uint8_t* top_mask, uint32_t* flags, hipStream_t stream);
+// The far pass over the m listed survivors, a wave each: every row of the window's box, its candidates across the lanes, until a dominator
+// is seen.  work (nullable, zeroed by the caller): += candidates tested.
+bool trees_filter_far(const TreeWindow& w, const HagGrid& g, const uint32_t* dir, const double* xs, const double* ys, const double* hs, const uint32_t* index,
+                      const uint32_t* survivors, uint32_t m, uint8_t* top_mask, unsigned long long* work, hipStream_t stream);
+// flags[i] = bytes[i] != 0 for i < n, flags[n] = 0
+bool trees_flags(const uint8_t* bytes, uint64_t n, uint32_t* flags, hipStream_t stream);
+// offsets = exclusive sum of flags: list[offsets[i]] = i and keys[offsets[i]] = the order-REVERSING image of h_i (of h_i + 0.0: the two
+// zeros get one key) for every flagged i
+bool trees_list(const TreesInput& in, const uint32_t* flags, const unsigned long long* offsets, uint64_t n, unsigned long long* keys, uint32_t* list, hipStream_t stream);
+// keys[i] = the key of point i's cell after its x and y were clamped into the grid's AABB, for a valid point (as trees_members) with
+// h >= floor; bit bits[0] + bits[1] alone for every other point.  vals[i] = i
+bool trees_query_keys(const TreesInput& in, double floor, const HagGrid& g, uint32_t* keys, uint32_t* vals, hipStream_t stream);
+// The crown search over the sorted queries: the top of smallest (d2, buffer index) within m2, by hag_search_kernel's ring walk with k = 1;
+// then ids[i] = number[at] iff d2 <= rc*rc && h >= exclusion*H, rc = half_factor*H, H = hs[at], else 0xFFFFFFFF (and for every point that is
+// no query).  counts[t] (nt zeroed entries) += the points labelled t, *labelled (zeroed) += all of them, folded per wave.
+bool trees_crown_search(const TreesInput& in, uint32_t n, const HagGrid& g, double m2, double half_factor, double exclusion, const uint32_t* query_keys,
+                        const uint32_t* query_order, const uint32_t* dir, const double* xs, const double* ys, const double* hs, const uint32_t* index,
+                        const uint32_t* number, uint32_t* ids, uint32_t* counts, unsigned long long* labelled, hipStream_t stream);
 
 }  // namespace pstk
