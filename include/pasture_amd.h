@@ -1272,6 +1272,70 @@ int pst_buffer_set_u8_from_ids_device(pst_buffer* b, const char* attribute_name,
  * LDS holds: measured at 4, 64, 512 and that many entries, the flat kernel was the faster one every time.  Host only. */
 int pst_crop_kernel_shape(uint32_t* flat_points_per_block, uint32_t* banded_points_per_block, uint32_t* flat_max_edges);
 
+/* ---- Segment statistics: per-label count, box, centroid, covariance and value statistics ------------------------------------------------
+ * The table of objects behind a segmentation -- lidR's crown_metrics, PCL's compute3DCentroid / computeCovarianceMatrix per cluster,
+ * CloudCompare's per-component statistics, PDAL's filters.stats with a `where` (the reference has nothing like it) -- for the labels of
+ * pst_euclidean_clusters, pst_dbscan, pst_region_growing, pst_segment_trees_device and pst_points_in_polygons_device, in ONE call for all
+ * segments.  Every operation below is a separately rounded f64 operation (no contraction); no square root appears anywhere.
+ *   inputs:      d_labels: DEVICE memory, len x u32.  n_segments = S.  v_i = the z of point i (d_values == NULL), or d_values[i]: DEVICE
+ *                memory, len x f64.  d_mask: DEVICE memory, len bytes, nullable.
+ *   member:      point i is a member of segment s = d_labels[i] iff s < S (0xFFFFFFFF and every label >= S belong to no segment and are
+ *                never used as an index), x, y and z are finite, v_i is finite, and d_mask is NULL or d_mask[i] != 0.  The members of s
+ *                in ascending buffer index are a_0 .. a_(m-1).
+ *   the sum:     every sum below is the fixed tree T (PST_SEGMENT_GROUP = 256 is part of this definition).  A sequence of length L > 1
+ *                is cut into consecutive groups of 256; missing elements of the last group are -0.0, the identity of IEEE addition in
+ *                round-to-nearest (it changes nothing, zero signs included: a group of one element is that element).  A group gives
+ *                r_l = ((g_l + g_(l+64)) + g_(l+128)) + g_(l+192) for l = 0 .. 63, then for h = 32, 16, 8, 4, 2, 1: r_l = r_l + r_(l+h)
+ *                for l < h; the group's partial is r_0.  The partials, in order, are the next sequence; repeat until one value is left
+ *                (at most 4 levels for any legal length).
+ *   statistics:  `stats` is a set of the bits below; 0 or a value above 255 -> PST_ERR_INVALID_ARGUMENT.  out = f64 [planes][S], the
+ *                planes of the set bits in ascending bit order.  Per segment with m > 0:
+ *                  PST_SEGMENT_COUNT (1)           1 plane   (double)m
+ *                  PST_SEGMENT_BOUNDS (2)          6 planes  min x, min y, min z, max x, max y, max z: each a member's bits, -0.0 below +0.0
+ *                  PST_SEGMENT_CENTROID (4)        3 planes  c_x = T(x) / (double)m, and y, z alike
+ *                  PST_SEGMENT_COVARIANCE (8)      6 planes  xx, xy, xz, yy, yz, zz: with d = p - c per component (the centroid above),
+ *                                                            T(d_a * d_b) / (double)m -- the population covariance, in two passes
+ *                  PST_SEGMENT_VALUE_MIN (16)      1 plane   the smallest v, -0.0 below +0.0
+ *                  PST_SEGMENT_VALUE_MAX (32)      1 plane   the largest v
+ *                  PST_SEGMENT_VALUE_MEAN (64)     1 plane   T(v) / (double)m
+ *                  PST_SEGMENT_VALUE_VARIANCE (128) 1 plane  T((v - mean) * (v - mean)) / (double)m
+ *                A segment without members has COUNT +0.0 and the canonical quiet NaN (0x7FF8000000000000) in every other plane.
+ *   apex:        u32 [S], nullable: per segment the lowest buffer index among the members whose v has the bits of VALUE_MAX (the top of
+ *                a tree, the ridge point of a roof); 0xFFFFFFFF for a segment without members.
+ *   results:     *n_members = the sum of the counts.  out and apex are BOTH in device memory (out_memkind = PST_MEM_DEVICE) or both in
+ *                host memory (anything else), the convention of the cluster labels.
+ * The result is a function of the points in buffer order, the labels, the values, the mask, S and `stats` alone -- not of the launch shape
+ * or the storage kind --, and two calls write the same bytes.  One path: the points are sorted by label with the library's stable radix
+ * sort (which is what makes "ascending buffer index" true), x, y, z and v are gathered into sorted columns, and one wave folds every group
+ * of 256, level by level; no floating-point atomics and no per-point atomics on per-segment records.
+ * Checks, in the order of pst_rasterize: null arguments (b, d_labels, out, n_members) and invalid parameters (stats, n_segments == 0, the
+ * memory kind) are answered before a device is looked for; then PST_ERR_MISSING_ATTRIBUTE when Position3D is not stored as Vec3f64; then
+ * the device (none: PST_ERR_NO_DEVICE, never a CPU path); then 2^32 - 16 points and more, or n_segments > 2^28 -> PST_ERR_UNSUPPORTED.  An
+ * empty buffer is legal: every segment is empty, and out and apex are filled with the empty values (which needs the device).  Out of
+ * device memory is PST_ERR_OUT_OF_MEMORY and the next call works.  Synchronous.  Interleaved or columnar, owned, sliced or external, at any
+ * byte offset.  Device scratch: 48 bytes per point (16 for the sort's pairs, 32 for the four columns; 40 without d_values) and the sort's
+ * own; 28 bytes per segment, 24 more for every further level of the tree, 8 per plane that the second pass needs and `stats` does not
+ * name, and the staging of host results; per group of 256 beyond a segment's first, 8 bytes per folded channel. */
+enum {
+  PST_SEGMENT_COUNT = 1,
+  PST_SEGMENT_BOUNDS = 2,
+  PST_SEGMENT_CENTROID = 4,
+  PST_SEGMENT_COVARIANCE = 8,
+  PST_SEGMENT_VALUE_MIN = 16,
+  PST_SEGMENT_VALUE_MAX = 32,
+  PST_SEGMENT_VALUE_MEAN = 64,
+  PST_SEGMENT_VALUE_VARIANCE = 128,
+  PST_SEGMENT_GROUP = 256
+};
+int pst_segment_statistics(const pst_buffer* b, const uint32_t* d_labels, uint32_t n_segments, const double* d_values, const uint8_t* d_mask, uint32_t stats, double* out,
+                           uint32_t* apex, uint32_t out_memkind, uint64_t* n_members);
+/* The kernels' seams (tests place their sizes around them; each pointer optional; host only): points per workgroup of the key and gather
+ * kernels, the group length of the sums (PST_SEGMENT_GROUP), groups per workgroup of the fold kernel (one wave each). */
+int pst_segments_kernel_shape(uint32_t* points_per_block, uint32_t* group, uint32_t* groups_per_block);
+/* Measurement aid.  With PST_SEGMENTS_TIMES=1 in the environment pst_segment_statistics brackets its three phases with stream events; this
+ * returns the calling thread's last call: ms = {keys + sort + directory, gather, folds + output}.  Zeros without the switch.  Host only. */
+int pst_segments_phase_times(double ms[3]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -26,6 +26,8 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          argsort_attribute, invert_order, morton_order, morton_sort, reorder_kernel_shape, reorder_phase_times, shuffle, shuffle_order,
                          sort_by_attribute, NO_POLYGON, PolygonSet, crop, crop_kernel_shape, overlay, points_in_polygons, polygon_mask,
                          NO_TREE, TreeSegmentation, TreeTops, extract_tree, segment_trees, segment_trees_device, tree_tops, tree_tops_device,
-                         trees_kernel_shape, trees_phase_times, trees_work)
+                         trees_kernel_shape, trees_phase_times, trees_work,
+                         NO_APEX, SEGMENT_STATS, SegmentTable, segment_planes, segment_statistics, segment_stats_bits, segments_kernel_shape,
+                         segments_phase_times)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

@@ -267,6 +267,9 @@ _PRODUCT_SIGNATURES = {
     "trees_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
     "trees_phase_times": [_D3],
     "trees_work": [_U64P],
+    "segment_statistics": [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _U64P],
+    "segments_kernel_shape": [_U32P, _U32P, _U32P],
+    "segments_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -1848,3 +1848,120 @@ def trees_work(api=None) -> dict:
     out = (C.c_uint64 * 3)()
     (api or product_api()).trees_work(out)
     return dict(zip(("candidates", "survivors", "far_tested"), (int(x) for x in out)))
+
+
+# ---- segment statistics: per-label count, box, centroid, covariance and value statistics (include/pasture_amd.h) ------------------------------
+
+# statistic name -> (bit of `stats`, planes); the planes come in ascending bit order
+SEGMENT_STATS = {"count": (1, 1), "bounds": (2, 6), "centroid": (4, 3), "covariance": (8, 6), "value_min": (16, 1), "value_max": (32, 1), "value_mean": (64, 1),
+                 "value_variance": (128, 1)}
+NO_APEX = 0xFFFFFFFF
+
+
+def segment_stats_bits(stats) -> int:
+    """the `stats` word of pst_segment_statistics for a name or an iterable of names of SEGMENT_STATS"""
+    names = [stats] if isinstance(stats, str) else list(stats)
+    unknown = [s for s in names if s not in SEGMENT_STATS]
+    if unknown:
+        raise ValueError(f"unknown statistics {unknown}: choose from {list(SEGMENT_STATS)}")
+    bits = 0
+    for s in names:
+        bits |= SEGMENT_STATS[s][0]
+    return bits
+
+
+def segment_planes(bits: int) -> int:
+    """the number of float64 planes of n_segments entries pst_segment_statistics writes for this `stats` word"""
+    return sum(planes for bit, planes in SEGMENT_STATS.values() if bits & bit)
+
+
+@dataclass(frozen=True)
+class SegmentTable:
+    """What segment_statistics returns, one row per segment; a statistic that was not asked for (and every array, when the planes went to
+    device memory) is None.  count (float64 [S]); min, max, centroid ([S][3]); covariance ([S][3][3], symmetric); value_min, value_max,
+    value_mean, value_variance ([S]); apex (uint32 [S], NO_APEX for a segment without members); n_members = count.sum().  A segment
+    without members has count 0 and NaN everywhere else."""
+    n_segments: int
+    n_members: int
+    count: Optional[np.ndarray] = None
+    min: Optional[np.ndarray] = None
+    max: Optional[np.ndarray] = None
+    centroid: Optional[np.ndarray] = None
+    covariance: Optional[np.ndarray] = None
+    value_min: Optional[np.ndarray] = None
+    value_max: Optional[np.ndarray] = None
+    value_mean: Optional[np.ndarray] = None
+    value_variance: Optional[np.ndarray] = None
+    apex: Optional[np.ndarray] = None
+
+    def principal_axes(self):
+        """(eigenvalues [S][3] ascending, eigenvectors [S][3][3] with the axes in the columns) of the covariance, by numpy.linalg.eigh on
+        the HOST: not part of the bit-exact contract of the table.  NaN for a segment without members."""
+        if self.covariance is None:
+            raise ValueError("principal_axes needs the 'covariance' statistic")
+        values, vectors = np.full((self.n_segments, 3), np.nan), np.full((self.n_segments, 3, 3), np.nan)
+        ok = np.isfinite(self.covariance).all(axis=(1, 2))
+        if ok.any():
+            values[ok], vectors[ok] = np.linalg.eigh(self.covariance[ok])
+        return values, vectors
+
+
+def segment_statistics(buffer: _Buffer, labels, n_segments: int, stats=("count", "bounds", "centroid"), values=None, mask=None, device_out_ptr: Optional[int] = None,
+                       device_apex_ptr: Optional[int] = None, return_apex: bool = False) -> SegmentTable:
+    """The table of objects behind a segmentation, in one call on the device: per segment s < n_segments the statistics `stats` names
+    (SEGMENT_STATS) over the points labelled s.  labels: a numpy integer array with one label per point (uploaded; -1 and 0xFFFFFFFF: no
+    segment) or the address of len(buffer) uint32 in DEVICE memory -- what euclidean_clusters, dbscan, region_growing, segment_trees and
+    points_in_polygons leave there.  values: None for z, a numpy float64 array or a DEVICE address (the heights above ground); mask: None, a
+    numpy uint8 array or a DEVICE address, only points with a non-zero byte take part.  A point with a coordinate or a value that is not
+    finite, or a label >= n_segments, belongs to no segment.  device_out_ptr: the planes go to DEVICE memory there, float64
+    [segment_planes(bits)][n_segments] in ascending bit order, and the apex (if any) to device_apex_ptr, uint32 [n_segments]; the table's
+    arrays are then None.  return_apex: also the apex, per segment the lowest index among its points of the largest value.  Every sum is
+    the fixed tree of the header, so the table is the same bytes whatever the storage or the launch shape."""
+    from .layout import PointAttributeDataType as T
+    bits = segment_stats_bits(stats)
+    S = int(n_segments)
+    api, n = buffer.api, buffer.len()
+    lptr, lheld = _device_input(api, labels, T.U32, np.uint32, n, "labels")
+    vptr, vheld = _device_input(api, values, T.F64, np.float64, n, "values")
+    mptr, mheld = _device_input(api, mask, T.U8, np.uint8, n, "mask")
+    members = C.c_uint64()
+    planes = segment_planes(bits)
+    if device_out_ptr is not None:
+        api.segment_statistics(buffer._h, C.c_void_p(lptr or None), S, C.c_void_p(vptr or None), C.c_void_p(mptr or None), bits, C.c_void_p(int(device_out_ptr) or None),
+                               C.c_void_p(int(device_apex_ptr or 0) or None), 0, C.byref(members))
+        del lheld, vheld, mheld
+        return SegmentTable(S, members.value)
+    host = np.full((planes, max(S, 0)), np.nan, dtype=np.float64)
+    apex = np.full(max(S, 0), NO_APEX, dtype=np.uint32) if return_apex else None
+    api.segment_statistics(buffer._h, C.c_void_p(lptr or None), S, C.c_void_p(vptr or None), C.c_void_p(mptr or None), bits, C.c_void_p(host.ctypes.data if host.size else 1),
+                           C.c_void_p(apex.ctypes.data) if apex is not None else None, 1, C.byref(members))
+    del lheld, vheld, mheld
+    fields, at = {}, 0
+    for name, (bit, count) in SEGMENT_STATS.items():
+        if bits & bit:
+            fields[name] = host[at:at + count]
+            at += count
+    out = {k: fields[k][0] for k in ("count", "value_min", "value_max", "value_mean", "value_variance") if k in fields}
+    if "bounds" in fields:
+        out["min"], out["max"] = np.ascontiguousarray(fields["bounds"][:3].T), np.ascontiguousarray(fields["bounds"][3:].T)
+    if "centroid" in fields:
+        out["centroid"] = np.ascontiguousarray(fields["centroid"].T)
+    if "covariance" in fields:
+        xx, xy, xz, yy, yz, zz = fields["covariance"]
+        out["covariance"] = np.stack([np.stack([xx, xy, xz], axis=1), np.stack([xy, yy, yz], axis=1), np.stack([xz, yz, zz], axis=1)], axis=1)
+    return SegmentTable(S, members.value, apex=apex, **out)
+
+
+def segments_kernel_shape(api=None) -> dict:
+    """The seams of the segment kernels: points per workgroup of the key and gather kernels, the group length of the sums (part of the
+    definition), groups per workgroup of the fold kernel (one wave each)."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).segments_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "group", "groups_per_block"), (x.value for x in v)))
+
+
+def segments_phase_times(api=None):
+    """(keys + sort + directory, gather, folds + output) in milliseconds of this thread's last segment_statistics call; zeros unless
+    PST_SEGMENTS_TIMES=1 was set when the library first ran one."""
+    return _phase_times(api, "segments_phase_times", 3)

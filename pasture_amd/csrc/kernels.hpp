@@ -585,4 +585,46 @@ bool trees_crown_search(const TreesInput& in, uint32_t n, const HagGrid& g, doub
                         const uint32_t* query_order, const uint32_t* dir, const double* xs, const double* ys, const double* hs, const uint32_t* index,
                         const uint32_t* number, uint32_t* ids, uint32_t* counts, unsigned long long* labelled, hipStream_t stream);
 
+// Segment statistics: per-label count, box, centroid, covariance and value statistics (segments.hip; the checks, the scratch and the order of
+// the launches are in segments_api.cpp).  The directory is raster.hip's (raster_directory_heads, then suffix_min_u32).  The seams
+// (pst_segments_kernel_shape):
+constexpr uint32_t kSegmentsPointsPerBlock = 256;  // points one workgroup of the key and gather kernels owns, one lane each
+constexpr uint32_t kSegmentGroup = 256;            // elements one wave folds: part of the DEFINITION (PST_SEGMENT_GROUP, include/pasture_amd.h)
+constexpr uint32_t kSegmentsGroupsPerBlock = 4;    // groups per workgroup of the fold kernel, ONE wave each
+enum : uint32_t { SG_COUNT = 1, SG_BOUNDS = 2, SG_CENTROID = 4, SG_COVARIANCE = 8, SG_VALUE_MIN = 16, SG_VALUE_MAX = 32, SG_VALUE_MEAN = 64, SG_VALUE_VARIANCE = 128 };
+// labels: one per point; values == nullptr: z; mask == nullptr: every point
+struct SegmentInput { const uint32_t* labels; const double* values; const uint8_t* mask; };
+// the output planes in device memory, S doubles per plane: count 1, min 3, max 3, centroid 3, covariance 6, the value's four 1 each; nullptr: not asked for
+struct SegmentPlanes { double *count, *min, *max, *centroid, *covariance, *value_min, *value_max, *value_mean, *value_variance; };
+// keys[i] = the label of a member, n_segments of every other point
+bool segment_keys(const Positions& pos, const SegmentInput& in, uint32_t n_segments, uint32_t* keys, hipStream_t stream);
+// x, y, z and the value (vs nullable: no values, the value is z) of point order[s] for the sorted positions s < dir[n_segments]
+bool segment_gather(const Positions& pos, const SegmentInput& in, const uint32_t* order, const uint32_t* dir, uint32_t n_segments, double* xs, double* ys, double* zs,
+                    double* vs, hipStream_t stream);
+// count[s] = members of s, groups[s] = ceil(count / 256), entry n_segments of both 0; the COUNT plane, and every other plane and the apex
+// (nullable) of a segment without members
+bool segment_counts(const uint32_t* dir, uint32_t n_segments, const SegmentPlanes& out, uint32_t* apex, uint32_t* count, uint32_t* groups, hipStream_t stream);
+// next_count[s] = groups[s] where that is more than one, else 0 (the segment is finished); next_groups = ceil(next_count / 256); n_segments + 1 entries
+bool segment_next_level(const uint32_t* groups, uint32_t n_segments, uint32_t* next_count, uint32_t* next_groups, hipStream_t stream);
+// One level of the fold.  count[s] elements of segment s start at element_offset[s] of every input array; group_offset = the exclusive sum of
+// ceil(count / 256) (n_segments + 1 entries, the last n_groups); partial_offset = the next level's element_offset, where a segment of more
+// than one group writes its partials.
+struct SegmentLevel { uint64_t n_groups; const unsigned long long *group_offset, *element_offset, *partial_offset; const uint32_t* count; };
+// A channel with a null input is not computed.  A segment of one group writes result[s] -- a sum divided by (double) of its members
+// (dir[s + 1] - dir[s]) --, every other its partials to `out`.  Sums: up to seven channels.  Minima and maxima: x y z v, read through the
+// ordered key; apex_in rides with max channel 3 (the lowest apex_in among the elements of the largest key).  results are nullable.
+// products: sum_in is not read; the elements of sums 0 .. 5 are the products xx xy xz yy yz zz of column[0 .. 2] - mean[0 .. 2][s], those of
+// sum 6 the square of column[3] - mean[3][s], for the sums whose result is not null (minima and maxima are not computed).
+struct SegmentFold {
+  SegmentLevel level;
+  const uint32_t* dir;
+  uint32_t n_segments;
+  const double* sum_in[7]; double* sum_out[7]; double* sum_result[7];
+  const double* min_in[4]; double* min_out[4]; double* min_result[4];
+  const double* max_in[4]; double* max_out[4]; double* max_result[4];
+  const uint32_t* apex_in; uint32_t* apex_out; uint32_t* apex_result;
+  const double* column[4]; const double* mean[4];
+};
+bool segment_fold(const SegmentFold& f, bool products, hipStream_t stream);
+
 }  // namespace pstk
