@@ -1336,6 +1336,65 @@ int pst_segments_kernel_shape(uint32_t* points_per_block, uint32_t* group, uint3
  * returns the calling thread's last call: ms = {keys + sort + directory, gather, folds + output}.  Zeros without the switch.  Host only. */
 int pst_segments_phase_times(double ms[3]);
 
+/* ---- Quantiles: per-cell and per-segment order statistics and counts above a threshold ---------------------------------------------------
+ * What lidR's zq95 and pzabove2, PDAL's filters.stats percentiles and numpy's quantile per group compute (the reference has nothing like
+ * it): the p-quantile of the values of every cell of an XY grid (pst_rasterize_quantiles) or of every segment (pst_segment_quantiles), and
+ * the number of values above a threshold, in ONE call for all groups.  Every operation below is a separately rounded f64 operation (no
+ * contraction).
+ *   groups:      pst_rasterize_quantiles: the cells of pst_rasterize's grid, with that call's grid rules (origin and dim given together or
+ *                both NULL: the automatic grid over the finite points, whatever the mask), its inside test and its members: x, y and v_i
+ *                finite, d_mask NULL or d_mask[i] != 0, inside.  groups = rows * cols, group = row * cols + col.
+ *                pst_segment_quantiles: the segments of pst_segment_statistics with its members: d_labels[i] < S, x, y, z and v_i finite,
+ *                d_mask NULL or d_mask[i] != 0.  groups = S.
+ *                v_i = the z of point i (d_values == NULL), or d_values[i]: DEVICE memory, len x f64.
+ *   order:       s_0 .. s_(m-1) are the values of a group's m members in ascending order of the key that orders the doubles
+ *                numerically with -0.0 below +0.0.  Values with equal bits are indistinguishable: there is no tie rule.
+ *   quantiles:   probs[0 .. n_probs): HOST doubles in [0, 1]; a NaN or anything outside -> PST_ERR_INVALID_ARGUMENT.  Per p:
+ *                  h = (double)(m - 1) * p,  lo = (uint32)floor(h),  g = h - (double)lo
+ *                  PST_QUANTILE_LINEAR (0)  s_lo with its bits when g == 0.0, else s_lo + g * (s_(lo+1) - s_lo)   (Hyndman-Fan type 7)
+ *                  PST_QUANTILE_LOWER (1)   s_lo
+ *                  PST_QUANTILE_HIGHER (2)  s_lo when g == 0.0, else s_(lo+1)
+ *                any other `method` -> PST_ERR_INVALID_ARGUMENT.  h <= m - 1 always (the exact product is at most a representable
+ *                number, and rounding is monotone); g > 0 means h is no integer, so h < m - 1 and lo + 1 <= m - 1.  p = 0 gives the bits
+ *                of the group's MIN, p = 1 the bits of its MAX (pst_rasterize's and pst_segment_statistics' planes).  Beyond this, what
+ *                IEEE arithmetic gives is the definition: a difference that overflows gives +-inf or a NaN.
+ *   above:       thresholds[0 .. n_thresholds): HOST doubles; a NaN -> PST_ERR_INVALID_ARGUMENT, +-inf is legal.  Per t: (double) the
+ *                number of members with v > t, COMPARED AS DOUBLES: -0.0 is not above +0.0, and +0.0 is not above -0.0.
+ *   output:      out = f64 [1 + n_probs + n_thresholds][groups]: plane 0 is COUNT = (double)m, then the quantile planes in the order of
+ *                probs, then the above planes in the order of thresholds; in device memory (out_memkind = PST_MEM_DEVICE) or host memory
+ *                (anything else).  1 <= n_probs + n_thresholds <= 64, else PST_ERR_INVALID_ARGUMENT.  An empty group has COUNT +0.0, the
+ *                canonical quiet NaN (0x7FF8000000000000) in every quantile plane and +0.0 in every above plane.
+ *   results:     *n_members = the sum of the counts; origin_out, dim_out (each optional) = the grid that was used.
+ * The result is a function of the MULTISET of (group, value) pairs and the parameters alone: not of the order of the points in the buffer,
+ * the storage kind, the launch shape or the path a group took.  Two calls write the same bytes.  Groups of at most PST_QUANTILES_CAP
+ * members are sorted in LDS, many per workgroup, and selected there; larger ones are sorted by two radix sorts (by value, then stably by
+ * group).  No floating-point atomics, and no per-point atomics on per-group records.
+ * Checks: those of pst_rasterize and of pst_segment_statistics respectively, in their order, with the plane count, the arrays, the
+ * probabilities, the method and the thresholds where `stats` is checked there; the same limits (2^32 - 16 points, 2^28 cells or segments),
+ * the same empty-buffer rules (automatic grid: PST_OK on the host, nothing written; a given grid or segments: every group empty) and the
+ * same out-of-memory behaviour.  Synchronous.  Interleaved or columnar, owned, sliced or external, at any byte offset.  Device scratch: 24
+ * bytes per point and the sort's own, 4 per group, the staging of host results, and 44 per member of a group above the cap (DESIGN.md
+ * 4.25). */
+enum {
+  PST_QUANTILE_LINEAR = 0,
+  PST_QUANTILE_LOWER = 1,
+  PST_QUANTILE_HIGHER = 2,
+  PST_QUANTILES_CAP = 512
+};
+int pst_rasterize_quantiles(const pst_buffer* b, const double* d_values, const uint8_t* d_mask, double cell_size, const double origin[2], const uint32_t dim[2],
+                            const double* probs, uint32_t n_probs, uint32_t method, const double* thresholds, uint32_t n_thresholds, double* out, uint32_t out_memkind,
+                            double origin_out[2], uint32_t dim_out[2], uint64_t* n_members);
+int pst_segment_quantiles(const pst_buffer* b, const uint32_t* d_labels, uint32_t n_segments, const double* d_values, const uint8_t* d_mask, const double* probs,
+                          uint32_t n_probs, uint32_t method, const double* thresholds, uint32_t n_thresholds, double* out, uint32_t out_memkind, uint64_t* n_members);
+/* The kernels' seams (tests place their sizes around them; each pointer optional; host only): the sorted positions whose groups one
+ * workgroup of the LDS kernel owns, the largest group it sorts (PST_QUANTILES_CAP), and the window of sorted positions it loads and sorts
+ * at once -- points_per_block + cap - 1 <= window, so a workgroup packs up to points_per_block groups. */
+int pst_quantiles_kernel_shape(uint32_t* points_per_block, uint32_t* cap, uint32_t* window);
+/* Measurement aid.  With PST_QUANTILES_TIMES=1 in the environment both calls bracket their four phases with stream events; this returns
+ * the calling thread's last call: ms = {keys + sort + directory, gather, counts + small groups, large groups}.  Zeros without the switch.
+ * Host only. */
+int pst_quantiles_phase_times(double ms[4]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

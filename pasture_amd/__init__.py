@@ -28,6 +28,7 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          NO_TREE, TreeSegmentation, TreeTops, extract_tree, segment_trees, segment_trees_device, tree_tops, tree_tops_device,
                          trees_kernel_shape, trees_phase_times, trees_work,
                          NO_APEX, SEGMENT_STATS, SegmentTable, segment_planes, segment_statistics, segment_stats_bits, segments_kernel_shape,
-                         segments_phase_times)
+                         segments_phase_times,
+                         QUANTILE_METHODS, SegmentQuantiles, quantiles_kernel_shape, quantiles_phase_times, rasterize_quantiles, segment_quantiles)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

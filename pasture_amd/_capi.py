@@ -270,6 +270,10 @@ _PRODUCT_SIGNATURES = {
     "segment_statistics": [_P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _U64P],
     "segments_kernel_shape": [_U32P, _U32P, _U32P],
     "segments_phase_times": [_D3],
+    "rasterize_quantiles": [_P, _P, _P, C.c_double, _D3, _U32P, _D3, C.c_uint32, C.c_uint32, _D3, C.c_uint32, _P, C.c_uint32, _D3, _U32P, _U64P],
+    "segment_quantiles": [_P, _P, C.c_uint32, _P, _P, _D3, C.c_uint32, C.c_uint32, _D3, C.c_uint32, _P, C.c_uint32, _U64P],
+    "quantiles_kernel_shape": [_U32P, _U32P, _U32P],
+    "quantiles_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -1965,3 +1965,115 @@ def segments_phase_times(api=None):
     """(keys + sort + directory, gather, folds + output) in milliseconds of this thread's last segment_statistics call; zeros unless
     PST_SEGMENTS_TIMES=1 was set when the library first ran one."""
     return _phase_times(api, "segments_phase_times", 3)
+
+
+# ---- quantiles: per-cell and per-segment order statistics and counts above a threshold (include/pasture_amd.h) -------------------------------
+
+QUANTILE_METHODS = {"linear": 0, "lower": 1, "higher": 2}
+
+
+def _quantile_request(probs, above, method):
+    """(probs, n, method word, thresholds, n) as the two quantile calls take them; a probability outside [0, 1] and a NaN are the library's to refuse"""
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f"unknown method {method!r}: choose from {list(QUANTILE_METHODS)}")
+    p = [float(x) for x in ([probs] if isinstance(probs, (int, float)) else probs)]
+    t = [float(x) for x in ([above] if isinstance(above, (int, float)) else above)]
+    return (C.c_double * max(len(p), 1))(*p), len(p), QUANTILE_METHODS[method], (C.c_double * max(len(t), 1))(*t), len(t)
+
+
+def rasterize_quantiles(buffer: _Buffer, cell_size: float, probs=(0.5,), above=(), method: str = "linear", values=None, device_mask_ptr: Optional[int] = None,
+                        origin=None, dim=None, device_out_ptr: Optional[int] = None) -> Raster:
+    """Per-cell quantiles and counts above a threshold on rasterize's grid, on the device.  probs: probabilities in [0, 1]; above: thresholds
+    (a value counts when it is greater, compared as doubles); method: "linear" (numpy's, R's and lidR's default), "lower" or "higher".
+    values, device_mask_ptr, origin and dim: what rasterize takes.  Raster.planes holds "count" (rows, cols), "quantiles" (P, rows, cols) in
+    the order of probs and "above" (T, rows, cols) in the order of above; an empty cell has count 0, NaN quantiles and 0 above.
+    device_out_ptr: float64 [1 + P + T][rows][cols] goes to DEVICE memory there and Raster.planes is empty.  The result does not depend on
+    the order of the points.  (Host planes on the automatic grid cost one pmf_grid call first, to size the arrays.)"""
+    c_probs, P, word, c_thr, Tn = _quantile_request(probs, above, method)
+    if (origin is None) != (dim is None):
+        raise ValueError("origin and dim must be given together or not at all")
+    held = None
+    if isinstance(values, PointAttributeDefinition):
+        held = _values_column(buffer, values)
+        values_ptr = held.ptr
+    else:
+        values_ptr = int(values) if values is not None else 0
+    c_origin = (C.c_double * 2)(*origin) if origin is not None else None
+    c_dim = (C.c_uint32 * 2)(*dim) if dim is not None else None
+    origin_out, dim_out, members = (C.c_double * 2)(), (C.c_uint32 * 2)(), C.c_uint64()
+    host = None
+    if device_out_ptr is None:
+        if dim is not None:
+            cols, rows = int(dim[0]), int(dim[1])
+        else:
+            grid = pmf_grid(buffer, cell_size)
+            cols, rows = grid["cols"], grid["rows"]
+        host = np.full((1 + P + Tn, rows, cols), np.nan, dtype=np.float64)
+        out_ptr, memkind = C.c_void_p(host.ctypes.data if host.size else 1), 1
+    else:
+        out_ptr, memkind = C.c_void_p(int(device_out_ptr) or None), 0
+    buffer.api.rasterize_quantiles(buffer._h, C.c_void_p(values_ptr or None), C.c_void_p(int(device_mask_ptr or 0) or None), cell_size, c_origin, c_dim, c_probs, P, word,
+                                   c_thr, Tn, out_ptr, memkind, origin_out, dim_out, C.byref(members))
+    del held
+    planes = {} if host is None else {"count": host[0], "quantiles": host[1:1 + P], "above": host[1 + P:]}
+    return Raster((origin_out[0], origin_out[1]), cell_size, dim_out[0], dim_out[1], members.value, planes)
+
+
+@dataclass(frozen=True)
+class SegmentQuantiles:
+    """What segment_quantiles returns: count (float64 [S]), quantiles ([P][S], in the order of probs), above ([T][S], in the order of the
+    thresholds) -- each None when the planes went to device memory -- and n_members = count.sum().  A segment without members has count
+    0, NaN quantiles and 0 above."""
+    n_segments: int
+    n_members: int
+    count: Optional[np.ndarray] = None
+    quantiles: Optional[np.ndarray] = None
+    above: Optional[np.ndarray] = None
+
+    def cover(self, t_index: int = 0):
+        """above[t_index] / count on the HOST: the share of a segment's values above that threshold (lidR's pzabove2 as a fraction); NaN
+        for a segment without members"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.above[t_index] / self.count
+
+
+def segment_quantiles(buffer: _Buffer, labels, n_segments: int, probs=(0.5,), above=(), method: str = "linear", values=None, mask=None,
+                      device_out_ptr: Optional[int] = None) -> SegmentQuantiles:
+    """Per-segment quantiles and counts above a threshold, in one call on the device.  labels, values and mask: what segment_statistics takes,
+    with its members; probs, above and method: what rasterize_quantiles takes.  device_out_ptr: float64 [1 + P + T][n_segments] goes to
+    DEVICE memory there and the arrays are None.  The result does not depend on the order of the points."""
+    from .layout import PointAttributeDataType as T
+    c_probs, P, word, c_thr, Tn = _quantile_request(probs, above, method)
+    S = int(n_segments)
+    api, n = buffer.api, buffer.len()
+    lptr, lheld = _device_input(api, labels, T.U32, np.uint32, n, "labels")
+    vptr, vheld = _device_input(api, values, T.F64, np.float64, n, "values")
+    mptr, mheld = _device_input(api, mask, T.U8, np.uint8, n, "mask")
+    members = C.c_uint64()
+    host = None
+    if device_out_ptr is None:
+        host = np.full((1 + P + Tn, max(S, 0)), np.nan, dtype=np.float64)
+        out_ptr, memkind = C.c_void_p(host.ctypes.data if host.size else 1), 1
+    else:
+        out_ptr, memkind = C.c_void_p(int(device_out_ptr) or None), 0
+    api.segment_quantiles(buffer._h, C.c_void_p(lptr or None), S, C.c_void_p(vptr or None), C.c_void_p(mptr or None), c_probs, P, word, c_thr, Tn, out_ptr, memkind,
+                          C.byref(members))
+    del lheld, vheld, mheld
+    if host is None:
+        return SegmentQuantiles(S, members.value)
+    return SegmentQuantiles(S, members.value, host[0], host[1:1 + P], host[1 + P:])
+
+
+def quantiles_kernel_shape(api=None) -> dict:
+    """The seams of the quantile kernels: the sorted positions whose groups one workgroup of the LDS kernel owns, the largest group it sorts
+    (larger ones take the two radix sorts), and the window of sorted positions it loads and sorts at once."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(3)]
+    (api or product_api()).quantiles_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("points_per_block", "cap", "window"), (x.value for x in v)))
+
+
+def quantiles_phase_times(api=None):
+    """(keys + sort + directory, gather, counts + small groups, large groups) in milliseconds of this thread's last rasterize_quantiles or
+    segment_quantiles call; zeros unless PST_QUANTILES_TIMES=1 was set when the library first ran one."""
+    return _phase_times(api, "quantiles_phase_times", 4)

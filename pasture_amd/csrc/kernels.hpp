@@ -627,4 +627,33 @@ struct SegmentFold {
 };
 bool segment_fold(const SegmentFold& f, bool products, hipStream_t stream);
 
+// Group order statistics: quantiles and counts above a threshold per cell or per segment (quantiles.hip; the checks, the scratch and the order
+// of the launches are in quantiles_api.cpp).  Keys, sort, directory and gather are raster.hip's and segments.hip's.  The seams
+// (pst_quantiles_kernel_shape):
+constexpr uint32_t kQuantilesPointsPerBlock = 1536;  // sorted positions whose groups one workgroup of the window kernel owns
+constexpr uint32_t kQuantilesCap = 512;              // the largest group the window kernel sorts in LDS; a larger one is listed
+constexpr uint32_t kQuantilesWindow = 2048;          // sorted positions one workgroup loads and sorts: >= points per block + cap - 1
+enum : uint32_t { QM_LINEAR = 0, QM_LOWER = 1, QM_HIGHER = 2 };
+// param: the probabilities, then the thresholds.  The output is out[1 + n_probs + n_thresholds][n_groups], plane 0 the COUNT
+struct QuantileRequest { double param[64]; uint32_t n_probs, n_thresholds, method; };
+// heavy_list and heavy_size: this many entries and one more
+size_t quantile_heavy_capacity(uint64_t n, uint64_t n_groups, uint32_t cap);
+// One lane per group: the COUNT plane; an empty group's planes (the canonical NaN, +0.0); a group of more than `cap` members is appended to
+// heavy_list with its size in heavy_size (*heavy_count, zeroed)
+bool quantile_groups(const uint32_t* dir, uint32_t n_groups, uint32_t cap, const QuantileRequest& rq, double* out, uint32_t* heavy_list, uint32_t* heavy_size,
+                     uint32_t* heavy_count, hipStream_t stream);
+// The planes of every group of 1 .. cap members (cap <= kQuantilesCap; 0: nothing to do).  sorted_keys[s] = the group of sorted position s
+// for s < dir[n_groups]; n = the length of both arrays
+bool quantile_small_groups(const double* sorted_values, const uint32_t* sorted_keys, const uint32_t* dir, uint32_t n, uint32_t n_groups, uint32_t cap,
+                           const QuantileRequest& rq, double* out, hipStream_t stream);
+// The listed groups, `heavy` of them, with heavy_offset = the exclusive sum of heavy_size (heavy + 1 entries, the last n_listed): the listed
+// members' keys, slots[j] = j and owner[j] = the place of j's group in the list
+bool quantile_heavy_compact(const double* sorted_values, const uint32_t* dir, const uint32_t* heavy_list, const unsigned long long* heavy_offset, uint32_t heavy,
+                            uint32_t n_listed, unsigned long long* keys, uint32_t* slots, uint32_t* owner, hipStream_t stream);
+// keys[r] = owner[slots[r]]
+bool quantile_owner_gather(const uint32_t* owner, const uint32_t* slots, uint32_t n, uint32_t* keys, hipStream_t stream);
+// ranked: the slots ordered by (owner, key).  One wave per listed group writes its planes
+bool quantile_heavy_select(const double* sorted_values, const uint32_t* dir, uint32_t n_groups, const uint32_t* heavy_list, const unsigned long long* heavy_offset,
+                           uint32_t heavy, const uint32_t* ranked, const QuantileRequest& rq, double* out, hipStream_t stream);
+
 }  // namespace pstk
