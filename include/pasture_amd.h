@@ -1395,6 +1395,50 @@ int pst_quantiles_kernel_shape(uint32_t* points_per_block, uint32_t* cap, uint32
  * Host only. */
 int pst_quantiles_phase_times(double ms[4]);
 
+/* ---- Fixed-radius neighbour search ----------------------------------------------------------------------------------------------------
+ * What PCL's radiusSearch, Open3D's search_radius_vector_3d, scipy's query_ball_point and PDAL's filters.radialdensity compute (the
+ * reference has nothing like it): ALL targets within `radius` of every query, as per-query counts (pst_radius_neighbour_counts_device)
+ * or as variable-length lists in CSR form (pst_radius_search_device), over a pst_nn_index, for queries from any buffer (the target's own
+ * buffer gives the self-search).  Every operation below is a separately rounded f64 operation (no contraction).
+ *   query:       q goes through the optional transform12 exactly as in the nearest-neighbour calls: x' = ((r00*x + r01*y) + r02*z) + t0.
+ *   neighbour:   a finite target p is a neighbour of q iff d2 = (dx*dx + dy*dy) + dz*dz <= r2, dx = p.x - q'.x (target minus query),
+ *                r2 = radius * radius.  The bound is inclusive.  A query whose transformed position is not finite has no neighbours;
+ *                targets that are not finite are never neighbours.  A query that is itself a target finds itself at distance 0 (DBSCAN's
+ *                and scipy's convention; there is no exclusion option).
+ *   counts:      counts[i] = the number of neighbours of query i, u32.
+ *   lists:       offsets = u64 [n + 1], the exclusive sum of the counts; total = offsets[n].  The list of query i is
+ *                indices[offsets[i] .. offsets[i + 1]): target BUFFER indices, u32, ordered by ascending (d2, buffer index);
+ *                distances[j] = sqrt(d2), correctly rounded, in the same order.
+ * The result is a function of the two clouds, the transform and the radius alone: not of the index's cell edge, the launch shape, the
+ * storage kind or the path a list took.  Two calls write the same bytes.  No floating-point atomics.
+ * pst_radius_neighbour_counts_device: d_counts (DEVICE, n x u32) and total (HOST) are each optional, not both NULL.
+ * pst_radius_search_device: d_offsets (DEVICE, n + 1 x u64) and total (HOST) are required; d_indices (DEVICE, capacity x u32), d_distances
+ *   (DEVICE, capacity x f64, optional).  d_indices == NULL with capacity == 0 is the COUNTING FORM: offsets and *total are written, nothing is
+ *   filled.  total > capacity -> PST_ERR_RANGE with d_offsets and *total written and not one byte of d_indices or d_distances touched (the
+ *   pst_plane_inliers convention: size the arrays from *total and call again).  total >= 2^32 - 16 -> PST_ERR_UNSUPPORTED after the count, with
+ *   offsets and total written.
+ * Checks, in the order of the nearest-neighbour calls: before a device is looked for, NULL arguments, a radius that is not finite or
+ * not > 0 or whose square is not a normal number (pst_dbscan's check on eps), a transform entry that is not finite ->
+ * PST_ERR_INVALID_ARGUMENT; a query without Position3D stored as Vec3f64 -> PST_ERR_MISSING_ATTRIBUTE; then the device; then the limit of
+ * 2^32 - 16 query points.  An empty query writes offsets[0] = 0 and total 0.  An index without a finite target gives all-zero counts.
+ * Out of device memory -> PST_ERR_OUT_OF_MEMORY, and the next call works.  Both calls are synchronous.  Interleaved or columnar, owned,
+ * sliced or external, at any byte offset.  Lists of at most PST_RADIUS_SORT_CAP entries are ordered in LDS, many per workgroup; longer
+ * ones by three stable radix sorts (index, d2, list).
+ * Device scratch: per query 28 bytes and the pair sort's own (keys and order of the cell-ordered queries, the counts), 8 more in the
+ * counts call (the offsets); per entry 8 bytes (the d2 keys), allocated once the total is known; per entry of a list above the cap 48
+ * bytes and the sorts' own, and 16 per such list, allocated once their number is known. */
+enum { PST_RADIUS_SORT_CAP = 512 };
+int pst_radius_neighbour_counts_device(const pst_nn_index* index, const pst_buffer* query, const double* transform12, double radius, uint32_t* d_counts, uint64_t* total);
+int pst_radius_search_device(const pst_nn_index* index, const pst_buffer* query, const double* transform12, double radius, uint64_t* d_offsets, uint32_t* d_indices,
+                             double* d_distances, uint64_t capacity, uint64_t* total);
+/* The kernels' seams (tests place their sizes around them; each pointer optional; host only): the queries one workgroup of the count and
+ * fill kernels owns, the longest list the LDS kernel orders (PST_RADIUS_SORT_CAP), the window of entries it loads and sorts at once, and
+ * the entry positions whose lists it owns -- sort_positions_per_block + sort_cap - 1 <= sort_window. */
+int pst_radius_kernel_shape(uint32_t* queries_per_block, uint32_t* sort_cap, uint32_t* sort_window, uint32_t* sort_positions_per_block);
+/* Measurement aid.  With PST_RADIUS_TIMES=1 in the environment both calls bracket their phases with stream events; this returns the
+ * calling thread's last call: ms = {query keys + sort, count + scan, fill, order}.  Zeros without the switch.  Host only. */
+int pst_radius_phase_times(double ms[4]);
+
 /* ---- LAS record encoder (the writer side of the hot path) ---------------------------- */
 /* RawLASWriter::write_points_default_layout, pasture-io/src/las/raw_writers.rs:203-363 (+ write_helpers.rs:10-55):
  * `src` holds points in the DEFAULT typed layout of `point_format` (LasPointFormatN::layout(), las_types.rs; interleaved or

@@ -29,6 +29,8 @@ from .algorithms import (AABB, calculate_bounds, calculate_bounds_async, compute
                          trees_kernel_shape, trees_phase_times, trees_work,
                          NO_APEX, SEGMENT_STATS, SegmentTable, segment_planes, segment_statistics, segment_stats_bits, segments_kernel_shape,
                          segments_phase_times,
-                         QUANTILE_METHODS, SegmentQuantiles, quantiles_kernel_shape, quantiles_phase_times, rasterize_quantiles, segment_quantiles)
+                         QUANTILE_METHODS, SegmentQuantiles, quantiles_kernel_shape, quantiles_phase_times, rasterize_quantiles, segment_quantiles,
+                         NO_NEIGHBOUR, RadiusNeighbours, radius_kernel_shape, radius_neighbour_counts, radius_phase_times, radius_search,
+                         radius_search_device)
 
 product_api()  # load libpasture_amd.so now: a missing HIP extension must fail loudly, not at first use

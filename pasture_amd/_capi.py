@@ -274,6 +274,10 @@ _PRODUCT_SIGNATURES = {
     "segment_quantiles": [_P, _P, C.c_uint32, _P, _P, _D3, C.c_uint32, C.c_uint32, _D3, C.c_uint32, _P, C.c_uint32, _U64P],
     "quantiles_kernel_shape": [_U32P, _U32P, _U32P],
     "quantiles_phase_times": [_D3],
+    "radius_neighbour_counts_device": [_P, _P, _D3, C.c_double, _P, _U64P],
+    "radius_search_device": [_P, _P, _D3, C.c_double, _P, _P, _P, C.c_uint64, _U64P],
+    "radius_kernel_shape": [_U32P, _U32P, _U32P, _U32P],
+    "radius_phase_times": [_D3],
 }
 
 PRODUCT_SYMBOLS = ["last_error"] + list(_SHARED_SIGNATURES) + list(_PRODUCT_SIGNATURES)

@@ -2077,3 +2077,102 @@ def quantiles_phase_times(api=None):
     """(keys + sort + directory, gather, counts + small groups, large groups) in milliseconds of this thread's last rasterize_quantiles or
     segment_quantiles call; zeros unless PST_QUANTILES_TIMES=1 was set when the library first ran one."""
     return _phase_times(api, "quantiles_phase_times", 4)
+
+
+# ---- fixed-radius neighbour search: counts and CSR lists (include/pasture_amd.h) ----------------------------------------------------------------
+
+NO_NEIGHBOUR = 0xFFFFFFFF
+
+
+@dataclass
+class RadiusNeighbours:
+    """The neighbour lists of radius_search in CSR form: the list of query i is indices[offsets[i]:offsets[i + 1]] (target buffer indices,
+    uint32, nearest first, equal distances by ascending index) with distances (float64, None when they were not asked for) alongside."""
+    offsets: np.ndarray
+    indices: np.ndarray
+    distances: Optional[np.ndarray]
+
+    @property
+    def counts(self) -> np.ndarray:
+        return np.diff(self.offsets).astype(np.uint32)
+
+    def list(self, i: int):
+        """(indices, distances) of query i; distances is None when they were not asked for"""
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.indices[a:b], None if self.distances is None else self.distances[a:b]
+
+    def to_padded(self, k: int) -> np.ndarray:
+        """uint32 (n, k): each list's k nearest, padded with 0xFFFFFFFF -- what geometric_features(knn=...) takes, so that features can be
+        computed over radius neighbourhoods.  A host helper."""
+        n = len(self.offsets) - 1
+        out = np.full((n, k), NO_NEIGHBOUR, dtype=np.uint32)
+        if n == 0 or k == 0 or len(self.indices) == 0:
+            return out
+        starts = self.offsets[:-1].astype(np.int64)
+        take = np.minimum(np.diff(self.offsets.astype(np.int64)), k)
+        rows = np.repeat(np.arange(n, dtype=np.int64), take)
+        cols = np.arange(rows.size, dtype=np.int64) - np.repeat(np.cumsum(take) - take, take)
+        out[rows, cols] = self.indices[np.repeat(starts, take) + cols]
+        return out
+
+
+def radius_neighbour_counts(query: _Buffer, target_or_index, radius: float, transform=None, device_counts_ptr: Optional[int] = None):
+    """The number of finite targets within `radius` of every point of `query` (sent through `transform` first, if given), the point itself
+    included when it is a target: a uint32 (n,) numpy array -- or, with device_counts_ptr (n x uint32 in DEVICE memory), written there, and
+    the total is returned.  target_or_index: a buffer, or a NearestNeighbourIndex built over it once and searched many times."""
+    from .layout import PointAttributeDataType as T
+    total = C.c_uint64()
+    counts = None if device_counts_ptr is not None else _DeviceArray(query.api, T.U32, query.len())
+    ptr = int(device_counts_ptr) if device_counts_ptr is not None else counts.ptr
+    with _IndexFor(target_or_index) as index:
+        query.api.radius_neighbour_counts_device(index._h, query._h, _transform12(transform), radius, C.c_void_p(ptr or None), C.byref(total))
+    return total.value if counts is None else counts.to_numpy()
+
+
+def radius_search_device(query: _Buffer, index: NearestNeighbourIndex, radius: float, offsets_ptr: int, indices_ptr: int, distances_ptr: int, capacity: int,
+                         transform=None) -> int:
+    """The neighbour lists in caller-owned DEVICE memory (addresses): offsets uint64 [n + 1] (required), indices uint32 [capacity], distances
+    float64 [capacity] (0 = not wanted).  Returns the total number of entries.  indices_ptr = 0 with capacity = 0 is the counting form: the
+    offsets are written and nothing is filled.  A total above capacity raises a PastureError (status 3) whose message carries the total,
+    with the offsets written and the two arrays untouched."""
+    from ._capi import PastureError
+    total = C.c_uint64()
+    p = lambda a: C.c_void_p(int(a) or None)  # noqa: E731
+    try:
+        query.api.radius_search_device(index._h, query._h, _transform12(transform), radius, p(offsets_ptr), p(indices_ptr), p(distances_ptr), capacity, C.byref(total))
+    except PastureError as e:
+        if e.code != 3:
+            raise
+        raise PastureError(3, f"{e} (total = {total.value})") from None
+    return total.value
+
+
+def radius_search(query: _Buffer, target_or_index, radius: float, transform=None, return_distances: bool = True) -> RadiusNeighbours:
+    """All finite targets within `radius` of every point of `query` (PCL's radiusSearch, scipy's query_ball_point) as a RadiusNeighbours.
+    The count first -- it checks every argument before anything is allocated --, then the arrays of exactly that size, then the lists."""
+    from .layout import PointAttributeDataType as T
+    n = query.len()
+    total = C.c_uint64()
+    with _IndexFor(target_or_index) as index:
+        query.api.radius_neighbour_counts_device(index._h, query._h, _transform12(transform), radius, None, C.byref(total))
+        offsets = _DeviceArray(query.api, T.U64, n + 1)
+        indices = _DeviceArray(query.api, T.U32, total.value)
+        distances = _DeviceArray(query.api, T.F64, total.value) if return_distances else None
+        # (an empty array has no address: with capacity 0 the call is the counting form, which is all that is left to do)
+        radius_search_device(query, index, radius, offsets.ptr, indices.ptr, distances.ptr if distances else 0, total.value if indices.ptr else 0, transform)
+    return RadiusNeighbours(offsets.to_numpy(), indices.to_numpy(), distances.to_numpy() if distances else None)
+
+
+def radius_kernel_shape(api=None) -> dict:
+    """The seams of the radius-search kernels: queries one workgroup of the count and fill kernels owns, the longest list the LDS kernel
+    orders (longer ones take the radix sorts), the window of entries it loads and sorts at once, and the entry positions whose lists it owns."""
+    from ._capi import product_api
+    v = [C.c_uint32() for _ in range(4)]
+    (api or product_api()).radius_kernel_shape(*[C.byref(x) for x in v])
+    return dict(zip(("queries_per_block", "sort_cap", "sort_window", "sort_positions_per_block"), (x.value for x in v)))
+
+
+def radius_phase_times(api=None):
+    """(query keys + sort, count + scan, fill, order) in milliseconds of this thread's last radius_neighbour_counts* or radius_search* call;
+    zeros unless PST_RADIUS_TIMES=1 was set when the library first ran one."""
+    return _phase_times(api, "radius_phase_times", 4)

@@ -656,4 +656,37 @@ bool quantile_owner_gather(const uint32_t* owner, const uint32_t* slots, uint32_
 bool quantile_heavy_select(const double* sorted_values, const uint32_t* dir, uint32_t n_groups, const uint32_t* heavy_list, const unsigned long long* heavy_offset,
                            uint32_t heavy, const uint32_t* ranked, const QuantileRequest& rq, double* out, hipStream_t stream);
 
+// Fixed-radius neighbour search over a pst_nn_index (radius.hip; the checks, the scratch and the order of the launches are in
+// radius_api.cpp).  Query keys and their sort are nn.hip's.  The seams (pst_radius_kernel_shape):
+constexpr uint32_t kRadiusQueriesPerBlock = 256;          // queries one workgroup of the count and fill kernels owns, one lane each
+constexpr uint32_t kRadiusSortCap = 512;                  // the longest list the window kernel orders in LDS; a longer one is listed
+constexpr uint32_t kRadiusSortWindow = 2048;              // entries one workgroup loads and sorts: >= positions per block + cap - 1
+constexpr uint32_t kRadiusSortPositionsPerBlock = 1536;   // entry positions whose lists one workgroup of the window kernel owns
+// The queries in the order of their cell keys (query_keys, query_order: nn_query_keys and the pair sort), the index's sorted arrays.
+struct RadiusSearch {
+  Positions pos; NnTransform t; NnGrid g; double radius, r2;
+  const unsigned long long* query_keys; const uint32_t* query_order;
+  const unsigned long long* keys; const double *xs, *ys, *zs; const uint32_t* target_index; uint32_t nf;
+};
+// counts[i] = the neighbours of query i (buffer order), every query
+bool radius_count(const RadiusSearch& a, uint32_t* counts, hipStream_t stream);
+// the same walk: query i writes the buffer index and the ordered key of d2 of its neighbours into [offsets[i], offsets[i + 1]), in walk order
+bool radius_fill(const RadiusSearch& a, const unsigned long long* offsets, uint32_t* indices, unsigned long long* d2_keys, hipStream_t stream);
+// Every list of 1 .. cap entries (cap <= kRadiusSortCap; 0: nothing to do) ordered by (d2 key, index) in place; distances (nullable) = sqrt(d2)
+bool radius_order_short(const unsigned long long* offsets, uint32_t n, uint64_t total, uint32_t cap, uint32_t* indices, const unsigned long long* d2_keys, double* distances,
+                        hipStream_t stream);
+// the lists of more than cap entries appended to long_list with their lengths in long_size (*long_count, zeroed)
+bool radius_list_long(const unsigned long long* offsets, uint32_t n, uint32_t cap, uint32_t* long_list, uint32_t* long_size, uint32_t* long_count, hipStream_t stream);
+// The listed lists, `n_long` of them, with long_offset = the exclusive sum of long_size (n_long + 1 entries, the last n_listed): the listed
+// entries' indices (twice: one copy is the first sort's input), d2 keys and owner[j] = the place of j's list in long_list
+bool radius_long_compact(const unsigned long long* offsets, const uint32_t* long_list, const unsigned long long* long_offset, uint32_t n_long, uint32_t n_listed,
+                         const uint32_t* indices, const unsigned long long* d2_keys, uint32_t* idx, uint32_t* idx_keys, unsigned long long* keys, uint32_t* owner,
+                         hipStream_t stream);
+// out[r] = keys[slots[r]] (64 bits) and out[r] = owner[slots[r]] (32 bits)
+bool radius_gather_u64(const unsigned long long* keys, const uint32_t* slots, uint32_t n, unsigned long long* out, hipStream_t stream);
+bool radius_gather_u32(const uint32_t* owner, const uint32_t* slots, uint32_t n, uint32_t* out, hipStream_t stream);
+// ranked: the slots ordered by (owner, d2 key, index), sorted_owner: their owners.  Entry r goes to its list's place r - long_offset[owner]
+bool radius_long_scatter(const unsigned long long* offsets, const uint32_t* long_list, const unsigned long long* long_offset, uint32_t n_listed, const uint32_t* ranked,
+                         const uint32_t* sorted_owner, const uint32_t* idx, const unsigned long long* keys, uint32_t* indices, double* distances, hipStream_t stream);
+
 }  // namespace pstk

@@ -120,6 +120,7 @@ pub const PST_MEM_DEVICE: u32 = 0;
 pub const PST_MEM_PINNED_HOST: u32 = 1;
 pub const PST_SAMPLE_SHUFFLED: u32 = 0;
 pub const PST_SAMPLE_INDEX_ORDER: u32 = 1;
+pub const PST_RADIUS_SORT_CAP: u32 = 512;
 
 #[link(name = "pasture_amd")]
 extern "C" {
