@@ -1,5 +1,6 @@
 // The host side of the cluster index, shared by the drivers of the neighbour-based algorithms (clusters_api.cpp, dbscan_api.cpp,
-// sample_api.cpp, nn_api.cpp; the bounds also by pmf_api.cpp, hag_api.cpp, raster_api.cpp and reorder_api.cpp).
+// sample_api.cpp, nn_api.cpp; the bounds also by pmf_api.cpp, hag_api.cpp, raster_api.cpp, quantiles_api.cpp and reorder_api.cpp).  Its
+// counterpart for 32-bit keys over a 2-D grid or over labels is the dense directory (dense_directory.hpp).
 //
 // "The cluster index" of a cloud: the AABB of its finite points, read back -> (host: a ClusterGrid, cluster_grid.hpp) -> cluster_keys -> the
 // 64-bit pair sort on bits[0] + bits[1] + bits[2] + 1 bits, which puts the nf finite points in cell order in front of the others -> nn_gather:

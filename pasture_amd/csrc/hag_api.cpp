@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "cluster_index.hpp"
+#include "dense_directory.hpp"
 #include "phase_events.hpp"
 
 using namespace pst;
@@ -81,46 +82,37 @@ int pst_height_above_ground_device(const pst_buffer* query, const pst_buffer* gr
   if (!pstk::hag_make_grid(bounds.min_x, bounds.min_y, bounds.max_x, bounds.max_y, edge, &grid))
     throw Error(PST_ERR_UNSUPPORTED, std::string(who) + ": the extent of the ground points overflows f64");
   const size_t cells = (size_t)grid.dim[0] * grid.dim[1];
-  const unsigned key_bits = grid.bits[0] + grid.bits[1] + 1;  // (the bit above the cell number: not in G / not finite)
 
-  // One block of scratch.  The three arrays a sort alternates between serve the ground sort and then the query sort (the gather and the
-  // directory are done with them by then, in stream order): keys a | keys b | values a, each max(len(ground), len(query)) words; then the
-  // ground order = the buffer index of every sorted position | x | y | z of G | the directory | the query order | sort and scan scratch |
-  // the unresolved count.
-  const size_t n_max = std::max(nq, ng_points);
-  size_t sort_g = 0, sort_q = 0, scan_bytes = 0;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_g, nullptr, nullptr, nullptr, nullptr, ng_points, key_bits, s, true));
-  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_q, nullptr, nullptr, nullptr, nullptr, nq, key_bits, s));
-  PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, scan_bytes, nullptr, cells + 1, s));
+  // One block of scratch.  The three arrays the directory's sort alternates between serve the query sort afterwards (the gather and the
+  // directory are done with them by then, in stream order), so each has max(len(ground), len(query)) words; then x | y | z of G | the query
+  // order | sort and scan scratch | the unresolved count.  ix.order = the ground-buffer index of every sorted position.
   ScratchLayout layout;
-  const size_t off_keys_a = layout.add(n_max * 4), off_keys_b = layout.add(n_max * 4), off_vals_a = layout.add(n_max * 4), off_gorder = layout.add(ng_points * 4);
-  const size_t off_xs = layout.add((size_t)ng * 8), off_ys = layout.add((size_t)ng * 8), off_zs = layout.add((size_t)ng * 8), off_dir = layout.add((cells + 1) * 4);
-  const size_t off_qorder = layout.add(nq * 4), off_tmp = layout.add(std::max(std::max(sort_g, sort_q), scan_bytes)), off_count = layout.add(256);
+  DenseDirectory ix;
+  ix.carve(layout, packed_keys(grid), cells, ng_points, std::max(nq, ng_points), s);
+  size_t sort_q = 0;
+  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_q, nullptr, nullptr, nullptr, nullptr, nq, ix.keys.bits, s));
+  const size_t off_xs = layout.add((size_t)ng * 8), off_ys = layout.add((size_t)ng * 8), off_zs = layout.add((size_t)ng * 8);
+  const size_t off_qorder = layout.add(nq * 4), off_tmp = layout.add(std::max(ix.tmp_bytes(), sort_q)), off_count = layout.add(256);
   Scratch scratch(layout, s, who);
-  uint32_t *keys_a = scratch.at<uint32_t>(off_keys_a), *keys_b = scratch.at<uint32_t>(off_keys_b), *vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t *gorder = scratch.at<uint32_t>(off_gorder), *dir = scratch.at<uint32_t>(off_dir), *qorder = scratch.at<uint32_t>(off_qorder);
+  ix.bind(scratch);
+  uint32_t* qorder = scratch.at<uint32_t>(off_qorder);
   double *xs = scratch.at<double>(off_xs), *ys = scratch.at<double>(off_ys), *zs = scratch.at<double>(off_zs);
   void* tmp = scratch.at<void>(off_tmp);
   unsigned long long* count = scratch.at<unsigned long long>(off_count);
 
-  // ---- the ground index
+  // ---- the ground index: the heads kernel looks at the ng members alone
   PST_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(*count), s));
-  PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (cells + 1) * 4, s));
-  if (!pstk::hag_ground_keys(gpos, d_ground_mask, grid, keys_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
-  size_t bytes = sort_g;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, gorder, ng_points, key_bits, s, true));
-  if (!pstk::hag_gather(gpos, gorder, ng, xs, ys, zs, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");
-  if (!pstk::hag_directory_heads(keys_b, ng, grid, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
-  bytes = scan_bytes;
-  PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, cells + 1, s));
+  ix.build(ng, tmp, s, who,
+           [&](uint32_t* keys) { if (!pstk::hag_ground_keys(gpos, d_ground_mask, grid, keys, s)) throw hip_failure(std::string(who) + ": key launch failed: "); },
+           [&] { if (!pstk::nn_gather(gpos, ix.order, ng, xs, ys, zs, s)) throw hip_failure(std::string(who) + ": gather launch failed: "); });
   events.mark(1, s);
   // ---- the queries in cell order
-  if (!pstk::hag_query_keys(qpos, grid, keys_a, vals_a, s)) throw hip_failure(std::string(who) + ": query key launch failed: ");
-  bytes = sort_q;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, qorder, nq, key_bits, s));
+  if (!pstk::hag_query_keys(qpos, grid, ix.keys_a, ix.vals_a, s)) throw hip_failure(std::string(who) + ": query key launch failed: ");
+  size_t bytes = sort_q;
+  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, ix.keys_a, ix.keys_b, ix.vals_a, qorder, nq, ix.keys.bits, s));
   events.mark(2, s);
   // ---- the search
-  if (!pstk::hag_search(qpos, grid, k, m2, keys_b, qorder, dir, xs, ys, zs, gorder, d_hag, d_ground_z, count, s)) throw hip_failure(std::string(who) + ": search launch failed: ");
+  if (!pstk::hag_search(qpos, grid, k, m2, ix.keys_b, qorder, ix.dir, xs, ys, zs, ix.order, d_hag, d_ground_z, count, s)) throw hip_failure(std::string(who) + ": search launch failed: ");
   events.mark(3, s);
   PST_HIP_CHECK(hipMemcpyAsync(&unresolved, count, sizeof(unresolved), hipMemcpyDeviceToHost, s));
   stream_sync(s);

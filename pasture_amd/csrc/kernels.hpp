@@ -360,11 +360,7 @@ size_t hag_bounds_partials_bytes(uint64_t n_ground_points);
 bool hag_bounds(const Positions& ground, const uint8_t* mask, void* partials, HagBounds* rec, hipStream_t stream);
 // keys[i] = (cy << bits[0]) | cx of ground point i, with bit bits[0] + bits[1] set when i is not in G
 bool hag_ground_keys(const Positions& ground, const uint8_t* mask, const HagGrid& g, uint32_t* keys, hipStream_t stream);
-// positions of the ng members of G in sorted order
-bool hag_gather(const Positions& ground, const uint32_t* order, uint32_t ng, double* xs, double* ys, double* zs, hipStream_t stream);
-// dir: cols * rows + 1 entries, every byte 0xFF on entry.  dir[cell] = first sorted position of every occupied cell, dir[cols * rows] = ng;
-// pstk::suffix_min_u32 over all of it then makes dir[c] the first sorted position whose cell is c or later
-bool hag_directory_heads(const uint32_t* sorted_keys, uint32_t ng, const HagGrid& g, uint32_t* dir, hipStream_t stream);
+// (the positions of G in sorted order: nn_gather; the directory: directory_heads, below)
 // keys[i] = the key of query i's cell after its x and y were clamped into the grid's AABB; bit bits[0] + bits[1] alone: not finite.  vals[i] = i
 bool hag_query_keys(const Positions& query, const HagGrid& g, uint32_t* keys, uint32_t* vals, hipStream_t stream);
 // The search.  query_keys / query_order: the sorted pairs.  hag[i] = q.z - zg, ground_z[i] = zg (each optional); *unresolved += the finite
@@ -398,9 +394,12 @@ bool raster_atomic_decode(const unsigned long long* min_keys, const unsigned lon
                           hipStream_t stream);
 // The sorted path.  keys[i] = row * cols + col of a member, nonmember_key (a power of two not below cols * rows) of every other point
 bool raster_keys(const Positions& pos, const RasterInput& in, const PmfGrid& g, uint32_t nonmember_key, uint32_t* keys, hipStream_t stream);
-// dir: cols * rows + 1 entries, every byte 0xFF on entry.  dir[cell] = first sorted position of every occupied cell, dir[cols * rows] = the
-// number of members; pstk::suffix_min_u32 over all of it then makes dir[c] the first sorted position whose cell is c or later
-bool raster_directory_heads(const uint32_t* sorted_keys, uint32_t n, uint32_t n_cells, uint32_t* dir, hipStream_t stream);
+// The heads of every dense directory (dense_directory.hpp drives it).  dir: groups + 1 entries, every byte 0xFF on entry; n >= 1 sorted keys.
+// The group of a key is (key >> bx) * cols + its low bx bits: the key itself with bx = 0, cols = 1 (a label, a row-major cell), the cell
+// cy * cols + cx of a HagGrid's packed (cy << bx) | cx.  A key whose group is `groups` or more is no member, and the members come first.
+// dir[group] = first sorted position of every occupied group, dir[groups] = the first position that holds no member (n: every entry is one);
+// pstk::suffix_min_u32 over all of it then makes dir[g] the first sorted position whose group is g or later
+bool directory_heads(const uint32_t* sorted_keys, uint32_t n, uint32_t bx, uint32_t cols, uint32_t groups, uint32_t* dir, hipStream_t stream);
 // sorted_values[s] = the value of point order[s], s < dir[n_cells]
 bool raster_gather(const Positions& pos, const RasterInput& in, const uint32_t* order, const uint32_t* dir, uint32_t n_cells, double* sorted_values, hipStream_t stream);
 // One lane per cell walks its segment of sorted_values; a cell of more than kRasterChunk members is appended to heavy_list (*heavy_count,
@@ -544,7 +543,7 @@ bool set_u8_from_ids(uint64_t addr, uint64_t stride, uint64_t n, const uint32_t*
                      hipStream_t stream);
 
 // Individual trees: the local-maximum filter and the crowns (trees.hip; the window in trees_window.hpp; the checks, the scratch and the order
-// of the launches in trees_api.cpp).  The index is hag.hip's -- the same keys, sort, dense directory and suffix minimum -- over the members a
+// of the launches in trees_api.cpp).  The index is the dense 2-D grid's (dense_grid_device.hpp, dense_directory.hpp) over the members a
 // byte selects, with the height of every member next to its x and y.  The seams (pst_trees_kernel_shape):
 constexpr uint32_t kTreesPointsPerBlock = 256;         // candidates one workgroup of the near pass owns, one lane each
 constexpr uint32_t kTreesSurvivorsPerBlock = 4;        // survivors one workgroup of the far pass owns, ONE wave each
@@ -578,7 +577,7 @@ bool trees_list(const TreesInput& in, const uint32_t* flags, const unsigned long
 // keys[i] = the key of point i's cell after its x and y were clamped into the grid's AABB, for a valid point (as trees_members) with
 // h >= floor; bit bits[0] + bits[1] alone for every other point.  vals[i] = i
 bool trees_query_keys(const TreesInput& in, double floor, const HagGrid& g, uint32_t* keys, uint32_t* vals, hipStream_t stream);
-// The crown search over the sorted queries: the top of smallest (d2, buffer index) within m2, by hag_search_kernel's ring walk with k = 1;
+// The crown search over the sorted queries: the top of smallest (d2, buffer index) within m2, by dense_grid_device.hpp's ring walk with k = 1;
 // then ids[i] = number[at] iff d2 <= rc*rc && h >= exclusion*H, rc = half_factor*H, H = hs[at], else 0xFFFFFFFF (and for every point that is
 // no query).  counts[t] (nt zeroed entries) += the points labelled t, *labelled (zeroed) += all of them, folded per wave.
 bool trees_crown_search(const TreesInput& in, uint32_t n, const HagGrid& g, double m2, double half_factor, double exclusion, const uint32_t* query_keys,
@@ -586,7 +585,7 @@ bool trees_crown_search(const TreesInput& in, uint32_t n, const HagGrid& g, doub
                         const uint32_t* number, uint32_t* ids, uint32_t* counts, unsigned long long* labelled, hipStream_t stream);
 
 // Segment statistics: per-label count, box, centroid, covariance and value statistics (segments.hip; the checks, the scratch and the order of
-// the launches are in segments_api.cpp).  The directory is raster.hip's (raster_directory_heads, then suffix_min_u32).  The seams
+// the launches are in segments_api.cpp).  The directory is dense_directory.hpp's.  The seams
 // (pst_segments_kernel_shape):
 constexpr uint32_t kSegmentsPointsPerBlock = 256;  // points one workgroup of the key and gather kernels owns, one lane each
 constexpr uint32_t kSegmentGroup = 256;            // elements one wave folds: part of the DEFINITION (PST_SEGMENT_GROUP, include/pasture_amd.h)
@@ -628,7 +627,7 @@ struct SegmentFold {
 bool segment_fold(const SegmentFold& f, bool products, hipStream_t stream);
 
 // Group order statistics: quantiles and counts above a threshold per cell or per segment (quantiles.hip; the checks, the scratch and the order
-// of the launches are in quantiles_api.cpp).  Keys, sort, directory and gather are raster.hip's and segments.hip's.  The seams
+// of the launches are in quantiles_api.cpp).  Keys and gather are raster.hip's and segments.hip's, the directory dense_directory.hpp's.  The seams
 // (pst_quantiles_kernel_shape):
 constexpr uint32_t kQuantilesPointsPerBlock = 1536;  // sorted positions whose groups one workgroup of the window kernel owns
 constexpr uint32_t kQuantilesCap = 512;              // the largest group the window kernel sorts in LDS; a larger one is listed

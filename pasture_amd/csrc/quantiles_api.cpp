@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "cluster_index.hpp"
+#include "dense_directory.hpp"
 #include "phase_events.hpp"
 
 using namespace pst;
@@ -51,22 +52,21 @@ uint64_t order_statistics(const pstk::Positions& pos, const pstk::RasterInput& i
   const bool out_on_device = out_memkind == PST_MEM_DEVICE;
   const size_t heavy_capacity = pstk::quantile_heavy_capacity(n, G, cap);
 
-  // the planes (host results only) | keys a | keys b | values a | the order = the buffer index of every sorted position | the values in sorted
-  // order | the directory | the large groups, their sizes, the sizes' exclusive sum, their number | sort and scan scratch
-  size_t sort_bytes = 0, suffix_bytes = 0, scan_bytes = 0;
-  if (n) PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, key_bits, s, true));
-  PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, suffix_bytes, nullptr, G + 1, s));
+  // the planes (host results only) | the directory, ix.order = the buffer index of every sorted position | the values in sorted order | the
+  // large groups, their sizes, the sizes' exclusive sum, their number | sort and scan scratch
+  size_t scan_bytes = 0;
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, heavy_capacity + 1, s));
   ScratchLayout layout;
   const size_t off_stage = layout.add(out_on_device ? 0 : G * 8 * n_planes);
-  const size_t off_keys_a = layout.add(n * 4), off_keys_b = layout.add(n * 4), off_vals_a = layout.add(n * 4), off_order = layout.add(n * 4);
-  const size_t off_values = layout.add(n * 8), off_dir = layout.add((G + 1) * 4);
+  DenseDirectory ix;
+  ix.carve(layout, plain_keys(key_bits), G, n, n, s);
+  const size_t off_values = layout.add(n * 8);
   const size_t off_heavy = layout.add((heavy_capacity + 1) * 4), off_heavy_size = layout.add((heavy_capacity + 1) * 4), off_heavy_offset = layout.add((heavy_capacity + 1) * 8);
-  const size_t off_heavy_count = layout.add(256), off_tmp = layout.add(std::max(sort_bytes, std::max(suffix_bytes, scan_bytes)));
+  const size_t off_heavy_count = layout.add(256), off_tmp = layout.add(std::max(ix.tmp_bytes(), scan_bytes));
   Scratch scratch(layout, s, who);
+  ix.bind(scratch);
   double* planes = out_on_device ? out : scratch.at<double>(off_stage);
-  uint32_t *keys_a = scratch.at<uint32_t>(off_keys_a), *keys_b = scratch.at<uint32_t>(off_keys_b), *vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t *order = scratch.at<uint32_t>(off_order), *dir = scratch.at<uint32_t>(off_dir);
+  uint32_t *keys_b = ix.keys_b, *order = ix.order, *dir = ix.dir;
   uint32_t *heavy_list = scratch.at<uint32_t>(off_heavy), *heavy_size = scratch.at<uint32_t>(off_heavy_size), *heavy_count = scratch.at<uint32_t>(off_heavy_count);
   unsigned long long* heavy_offset = scratch.at<unsigned long long>(off_heavy_offset);
   double* values = scratch.at<double>(off_values);
@@ -75,17 +75,7 @@ uint64_t order_statistics(const pstk::Positions& pos, const pstk::RasterInput& i
   // ---- keys, sort, directory
   events.mark(0, s);
   PST_HIP_CHECK(hipMemsetAsync(heavy_count, 0, sizeof(*heavy_count), s));
-  if (n == 0) {
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0, (G + 1) * 4, s));  // every group is empty
-  } else {
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (G + 1) * 4, s));
-    fill_keys(keys_a);
-    size_t bytes = sort_bytes;
-    PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, order, n, key_bits, s, true));
-    if (!pstk::raster_directory_heads(keys_b, (uint32_t)n, (uint32_t)G, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
-    bytes = suffix_bytes;
-    PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, G + 1, s));
-  }
+  ix.build(tmp, s, who, fill_keys);
   events.mark(1, s);
   // ---- gather
   if (n && !pstk::raster_gather(pos, in, order, dir, (uint32_t)G, values, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");

@@ -11,7 +11,7 @@
 //            the maximum (a cell's max key only ever INCREASES, so "my key is not above what I read" implies "not above the final maximum"),
 //            a 32-bit atomicAdd per member; then one decode pass into the planes.  All three are order-free.
 //   sorted   key = row * cols + col (one more bit: not a member), the stable radix sort with the point index as payload -- so a cell's
-//            segment is in buffer-index order --, the dense directory of hag.hip, the values gathered into sorted order, and ONE LANE PER CELL
+//            segment is in buffer-index order --, the dense directory (dense_directory.hpp), the values gathered into sorted order, and ONE LANE PER CELL
 //            walking its segment: neighbouring lanes read neighbouring segments.  A cell of at most one chunk is all of its sum.  A cell of
 //            more is listed and taken by a workgroup: thread t sums chunks t, t + 256, ... each sequentially into scratch, one lane folds the
 //            partials in order, and the same again for SS once the mean is known -- the dependent chain of a cell of m members is
@@ -127,17 +127,21 @@ __global__ __launch_bounds__(kBlock) void raster_key_kernel(Pos pos, uint64_t n,
   keys[i] = member_cell(pos, i, in, g, cell, v) ? cell : nonmember_key;
 }
 
-__global__ __launch_bounds__(kBlock) void raster_heads_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t n_cells, uint32_t* __restrict__ dir) {
+// The heads of every dense directory (pstk::directory_heads).  A key's group: (key >> bx) * cols + the low bx bits -- a label or a row-major
+// cell is its own group (bx = 0, cols = 1), a packed (cy << bx) | cx its cell cy * cols + cx.
+__global__ __launch_bounds__(kBlock) void directory_heads_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t bx, uint32_t cols, uint32_t groups,
+                                                                 uint32_t* __restrict__ dir) {
   const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
   if (s >= n) return;
   const uint32_t key = keys[s];
-  const bool is_member = key < n_cells;  // (a member's key is its cell; every other key is a power of two not below n_cells)
+  const uint32_t group = (key >> bx) * cols + (key & ((1u << bx) - 1u));
+  const bool is_member = group < groups;  // (every other key is a power of two whose group is not below `groups`)
   const bool head = s == 0 || key != keys[s - 1];
   if (is_member) {
-    if (head) dir[key] = s;
-    if (s == n - 1) dir[n_cells] = n;  // every point is a member
+    if (head) dir[group] = s;
+    if (s == n - 1) dir[groups] = n;  // every entry is a member
   } else if (head) {
-    dir[n_cells] = s;  // the first point that is not one
+    dir[groups] = s;  // the first entry that is not one
   }
 }
 
@@ -357,8 +361,8 @@ bool raster_keys(const Positions& pos, const RasterInput& in, const PmfGrid& g, 
   return launched();
 }
 
-bool raster_directory_heads(const uint32_t* sorted_keys, uint32_t n, uint32_t n_cells, uint32_t* dir, hipStream_t stream) {
-  hipLaunchKernelGGL(raster_heads_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, sorted_keys, n, n_cells, dir);
+bool directory_heads(const uint32_t* sorted_keys, uint32_t n, uint32_t bx, uint32_t cols, uint32_t groups, uint32_t* dir, hipStream_t stream) {
+  hipLaunchKernelGGL(directory_heads_kernel, dim3(blocks_of(n, kBlock)), dim3(kBlock), 0, stream, sorted_keys, n, bx, cols, groups, dir);
   return launched();
 }
 

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "cluster_index.hpp"
+#include "dense_directory.hpp"
 #include "phase_events.hpp"
 
 using namespace pst;
@@ -121,35 +122,27 @@ int pst_rasterize(const pst_buffer* b, const double* d_values, const uint8_t* d_
     if (!out_on_device) PST_HIP_CHECK(hipMemcpyAsync(out, scratch.at<double>(off_stage), cells * 8 * n_planes, hipMemcpyDeviceToHost, s));
     stream_sync(s);
   } else {
-    // the planes (host results only) | keys a | keys b | values a | the order = the buffer index of every sorted position | the values in
-    // sorted order | the directory | the heavy cells | their number | their chunk partials | sort and scan scratch
+    // the planes (host results only) | the directory, ix.order = the buffer index of every sorted position | the values in sorted order | the
+    // heavy cells | their number | their chunk partials | sort and scan scratch
     const unsigned cell_bits = pstk::bits_for(cells);
     const uint32_t nonmember_key = 1u << cell_bits;  // at most 2^28
-    size_t sort_bytes = 0, scan_bytes = 0;
-    PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, cell_bits + 1, s, true));
-    PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, scan_bytes, nullptr, cells + 1, s));
-    const size_t off_keys_a = layout.add(n * 4), off_keys_b = layout.add(n * 4), off_vals_a = layout.add(n * 4), off_order = layout.add(n * 4);
-    const size_t off_values = layout.add(n * 8), off_dir = layout.add((cells + 1) * 4), off_heavy = layout.add((n / (pstk::kRasterChunk + 1) + 1) * 4);
-    const size_t off_heavy_count = layout.add(256), off_partials = layout.add(pstk::raster_partials_bytes(n)), off_tmp = layout.add(std::max(sort_bytes, scan_bytes));
+    DenseDirectory ix;
+    ix.carve(layout, plain_keys(cell_bits + 1), cells, n, n, s);
+    const size_t off_values = layout.add(n * 8), off_heavy = layout.add((n / (pstk::kRasterChunk + 1) + 1) * 4);
+    const size_t off_heavy_count = layout.add(256), off_partials = layout.add(pstk::raster_partials_bytes(n)), off_tmp = layout.add(ix.tmp_bytes());
     Scratch scratch(layout, s, who);
+    ix.bind(scratch);
     const pstk::RasterPlanes planes = planes_at(out_on_device ? out : scratch.at<double>(off_stage), stats, cells);
-    uint32_t *keys_a = scratch.at<uint32_t>(off_keys_a), *keys_b = scratch.at<uint32_t>(off_keys_b), *vals_a = scratch.at<uint32_t>(off_vals_a);
-    uint32_t *order = scratch.at<uint32_t>(off_order), *dir = scratch.at<uint32_t>(off_dir), *heavy = scratch.at<uint32_t>(off_heavy);
-    uint32_t* heavy_count = scratch.at<uint32_t>(off_heavy_count);
+    uint32_t *dir = ix.dir, *heavy = scratch.at<uint32_t>(off_heavy), *heavy_count = scratch.at<uint32_t>(off_heavy_count);
     double *values = scratch.at<double>(off_values), *partials = scratch.at<double>(off_partials);
-    void* tmp = scratch.at<void>(off_tmp);
     // ---- keys, sort, directory
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (cells + 1) * 4, s));
     PST_HIP_CHECK(hipMemsetAsync(heavy_count, 0, sizeof(*heavy_count), s));
-    if (!pstk::raster_keys(pos, in, grid, nonmember_key, keys_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
-    size_t bytes = sort_bytes;
-    PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, order, n, cell_bits + 1, s, true));
-    if (!pstk::raster_directory_heads(keys_b, (uint32_t)n, (uint32_t)cells, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
-    bytes = scan_bytes;
-    PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, cells + 1, s));
+    ix.build(scratch.at<void>(off_tmp), s, who, [&](uint32_t* keys) {
+      if (!pstk::raster_keys(pos, in, grid, nonmember_key, keys, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
+    });
     events.mark(2, s);
     // ---- reduction and output
-    if (!pstk::raster_gather(pos, in, order, dir, (uint32_t)cells, values, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");
+    if (!pstk::raster_gather(pos, in, ix.order, dir, (uint32_t)cells, values, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");
     if (!pstk::raster_reduce(values, dir, (uint32_t)cells, stats, planes, heavy, heavy_count, s)) throw hip_failure(std::string(who) + ": reduction launch failed: ");
     if (!pstk::raster_reduce_heavy(values, dir, (uint32_t)n, (uint32_t)cells, stats, planes, heavy, heavy_count, partials, s))
       throw hip_failure(std::string(who) + ": heavy-cell launch failed: ");

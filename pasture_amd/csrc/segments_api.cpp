@@ -4,7 +4,7 @@
 #include <memory>
 #include <vector>
 
-#include "cluster_index.hpp"
+#include "dense_directory.hpp"
 #include "phase_events.hpp"
 
 using namespace pst;
@@ -179,27 +179,25 @@ int pst_segment_statistics(const pst_buffer* b, const uint32_t* d_labels, uint32
   const bool sum_xyz = stats & (pstk::SG_CENTROID | pstk::SG_COVARIANCE), sum_v = stats & (pstk::SG_VALUE_MEAN | pstk::SG_VALUE_VARIANCE);
   const bool max_v = (stats & pstk::SG_VALUE_MAX) || apex;
 
-  // the planes and the apex (host results only) | the centroid and the mean where the second pass needs what `stats` does not name | keys a |
-  // keys b | values a | the order = the buffer index of every sorted position | x, y, z, v in sorted order | the directory | sort and scan scratch
-  const unsigned key_bits = pstk::bits_for(S + 1);  // the keys 0 .. S
-  size_t sort_bytes = 0, suffix_bytes = 0, scan_bytes = 0;
-  if (n) PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, n, key_bits, s, true));
-  PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, suffix_bytes, nullptr, S + 1, s));
+  // the planes and the apex (host results only) | the centroid and the mean where the second pass needs what `stats` does not name | the
+  // directory over the keys 0 .. S, ix.order = the buffer index of every sorted position | x, y, z, v in sorted order | sort and scan scratch
+  size_t scan_bytes = 0;
   PST_HIP_CHECK(pstk::exclusive_sum_u32_u64(nullptr, scan_bytes, nullptr, nullptr, S + 1, s));
   ScratchLayout layout;
   const size_t off_stage = layout.add(out_on_device ? 0 : S * 8 * n_planes), off_stage_apex = layout.add(out_on_device || !apex ? 0 : S * 4);
   const size_t off_centroid = layout.add(covariance && !(stats & pstk::SG_CENTROID) ? S * 8 * 3 : 0);
   const size_t off_mean = layout.add(variance && !(stats & pstk::SG_VALUE_MEAN) ? S * 8 : 0);
-  const size_t off_keys_a = layout.add(n * 4), off_keys_b = layout.add(n * 4), off_vals_a = layout.add(n * 4), off_order = layout.add(n * 4);
+  DenseDirectory ix;
+  ix.carve(layout, plain_keys(pstk::bits_for(S + 1)), S, n, n, s);
   const size_t off_xs = layout.add(n * 8), off_ys = layout.add(n * 8), off_zs = layout.add(n * 8), off_vs = layout.add(d_values ? n * 8 : 0);
-  const size_t off_dir = layout.add((S + 1) * 4), off_tmp = layout.add(std::max(sort_bytes, std::max(suffix_bytes, scan_bytes)));
+  const size_t off_tmp = layout.add(std::max(ix.tmp_bytes(), scan_bytes));
   Scratch scratch(layout, s, who);
+  ix.bind(scratch);
   const pstk::SegmentPlanes planes = planes_at(out_on_device ? out : scratch.at<double>(off_stage), stats, S);
   uint32_t* apex_dev = !apex ? nullptr : out_on_device ? apex : scratch.at<uint32_t>(off_stage_apex);
   double* centroid = stats & pstk::SG_CENTROID ? planes.centroid : covariance ? scratch.at<double>(off_centroid) : nullptr;
   double* mean = stats & pstk::SG_VALUE_MEAN ? planes.value_mean : variance ? scratch.at<double>(off_mean) : nullptr;
-  uint32_t *keys_a = scratch.at<uint32_t>(off_keys_a), *keys_b = scratch.at<uint32_t>(off_keys_b), *vals_a = scratch.at<uint32_t>(off_vals_a);
-  uint32_t *order = scratch.at<uint32_t>(off_order), *dir = scratch.at<uint32_t>(off_dir);
+  uint32_t *order = ix.order, *dir = ix.dir;
   double *xs = scratch.at<double>(off_xs), *ys = scratch.at<double>(off_ys), *zs = scratch.at<double>(off_zs);
   double* vs = d_values ? scratch.at<double>(off_vs) : zs;
   void* tmp = scratch.at<void>(off_tmp);
@@ -207,17 +205,9 @@ int pst_segment_statistics(const pst_buffer* b, const uint32_t* d_labels, uint32
 
   // ---- keys, sort, directory
   events.mark(0, s);
-  if (n == 0) {
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0, (S + 1) * 4, s));  // every segment is empty
-  } else {
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (S + 1) * 4, s));
-    if (!pstk::segment_keys(pos, in, n_segments, keys_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
-    size_t bytes = sort_bytes;
-    PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, order, n, key_bits, s, true));
-    if (!pstk::raster_directory_heads(keys_b, (uint32_t)n, n_segments, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
-    bytes = suffix_bytes;
-    PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, S + 1, s));
-  }
+  ix.build(tmp, s, who, [&](uint32_t* keys) {
+    if (!pstk::segment_keys(pos, in, n_segments, keys, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
+  });
   events.mark(1, s);
   // ---- gather
   if (n && !pstk::segment_gather(pos, in, order, dir, n_segments, xs, ys, zs, d_values ? vs : nullptr, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");

@@ -5,11 +5,10 @@
 // j is in i's window iff dx*dx + dy*dy <= r_i*r_i, dx = x_j - x_i, dy = y_j - y_i; j DOMINATES i iff h_j > h_i, or h_j == h_i and j < i in
 // buffer order.  Candidate i is a top iff no other candidate in ITS window dominates it.  Every operation a separately rounded f64 operation.
 //
-// The index is hag.hip's with another member set and a third column: the members a byte selects, sorted by cell key -- key = (cy << bx) | cx,
-// cell = trunc((v - min) / edge) per axis over the members' AABB (hag_grid.hpp) -- x, y, h as three f64 arrays next to the buffer index of
-// every sorted position, and the DENSE directory: the cells [x0, x1] of row y are the sorted positions dir[y * cols + x0] ..
-// dir[y * cols + x1 + 1].  The sort, the directory heads and the suffix minimum are the library's launches; the member pass, the keys and
-// the gather are here because the height may come from a column and z must then not be looked at (hag.hip's test all three components).
+// The index is dense_grid_device.hpp's over the members a byte selects, with a third column: x, y, h as three f64 arrays next to the buffer
+// index of every sorted position, and the dense directory.  The sort, the directory heads and the suffix minimum are the library's launches
+// (dense_directory.hpp); the member pass, the keys and the gather are here because the height may come from a column and z must then not be
+// looked at (hag.hip's test all three components).
 //
 // The filter, exactness.  A dominator of i is a candidate in i's window.  trees_window.hpp argues from the roundings of the predicate that
 // every point the ROUNDED predicate accepts lies in a cell of the box trees_window_cells returns, whatever the edge (its steps 1 - 5).  The
@@ -22,14 +21,12 @@
 // wave's lanes -- neighbours in cell order -- leave early together.  A top must see its whole window: hundreds of candidates, which one lane
 // would walk with 63 idle beside it; the far pass gives it a wave, the lanes across a row's candidates.
 //
-// The crown search, exactness.  It is hag_search_kernel's walk with k = 1, the list's only slot in registers, over an index of the tops:
-// the ring argument at the head of hag.hip (clamping, cells, margin, kth best, a dim of 1, rmax) holds word for word with "ground point"
-// read as "top", G as T and last.d2 as the best d2 so far, which starts at m2 = rc_max * rc_max.  Nothing of it is restated here.  What is
-// new is the bound: rc_t = half_factor * H_t and rc_max = half_factor * max |H|.  Multiplication by a fixed non-negative factor and squaring
-// of |.| are monotone under rounding, so rc_t*rc_t <= rc_max*rc_max = m2 for every top: a top beyond m2 fails its own test d2 <= rc_t*rc_t,
-// and when the nearest top of all lies beyond m2 the point is unlabelled either way.  (max |H|, not max H: a top of negative height has a
-// positive rc*rc too.)
-#include "positions_device.hpp"
+// The crown search, exactness.  It is the ring walk of dense_grid_device.hpp with k = 1 over an index of the tops, the bound B the best d2
+// so far, which starts at m2 = rc_max * rc_max: the argument there covers it.  What is new is the bound: rc_t = half_factor * H_t and
+// rc_max = half_factor * max |H|.  Multiplication by a fixed non-negative factor and squaring of |.| are monotone under rounding, so
+// rc_t*rc_t <= rc_max*rc_max = m2 for every top: a top beyond m2 fails its own test d2 <= rc_t*rc_t, and when the nearest top of all lies
+// beyond m2 the point is unlabelled either way.  (max |H|, not max H: a top of negative height has a positive rc*rc too.)
+#include "dense_grid_device.hpp"
 
 using namespace pstd;
 
@@ -64,27 +61,9 @@ __device__ __forceinline__ void load_xyh(const In& in, uint64_t i, double& x, do
 __device__ __forceinline__ bool valid(const In& in, uint64_t i, double x, double y, double h) {
   return finite(x) && finite(y) && finite(h) && (!in.mask || in.mask[i]);
 }
-__device__ __forceinline__ uint32_t cell_of(double v, double mn, double edge, uint32_t dim) {
-  const double q = (v - mn) / edge;
-  const uint32_t c = (uint32_t)q;  // 0 <= q < 2^21: the conversion truncates
-  return c < dim ? c : dim - 1;    // (never taken: hag_grid.hpp sized dim by this expression)
-}
-__device__ __forceinline__ double clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ bool dominates(double hj, uint32_t j, double hi, uint32_t i) { return hj > hi || (hj == hi && j < i); }
 
 // ---- members: the byte, and the block partials of their bounds ------------------------------------------------------------------------------
-// minima and maxima of finite values and an integer count: the order of the fold cannot matter
-__device__ __forceinline__ void block_fold(double (&mn)[3], double (&mx)[3], unsigned long long& c, double* sv, unsigned long long* sc) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) c = c + shfl_xor_any(c, off);
-  if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = c;
-  block_reduce_minmax<double, 3>(mn, mx, sv);  // (its barrier publishes sc as well)
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (uint32_t w = 1; w < kBlock / 64; ++w) c = c + sc[w];
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void trees_members_kernel(In in, uint64_t n, const uint8_t* __restrict__ also, double floor, uint8_t* __restrict__ member,
                                                                Bounds* __restrict__ partials) {
   __shared__ double sv[4 * 2 * 3];
@@ -133,11 +112,10 @@ __global__ __launch_bounds__(kBlock) void trees_key_kernel(Pos pos, const uint32
   const uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= count) return;
   const uint64_t i = subset ? subset[e] : e;
-  uint32_t key = 1u << (g.bits[0] + g.bits[1]);  // no member: behind every member
+  uint32_t key = no_member_key(g);
   if (!member || member[i]) {
     cgptr_t q = pos.base + i * pos.stride;
-    const double x = load_un<double>(q), y = load_un<double>(q + 8);
-    key = (cell_of(y, g.min[1], g.edge, g.dim[1]) << g.bits[0]) | cell_of(x, g.min[0], g.edge, g.dim[0]);
+    key = member_key(load_un<double>(q), load_un<double>(q + 8), g);
   }
   keys[e] = key;
 }
@@ -248,10 +226,7 @@ __global__ __launch_bounds__(kBlock) void trees_query_key_kernel(In in, uint64_t
   if (i >= n) return;
   double x, y, h;
   load_xyh(in, i, x, y, h);
-  uint32_t key = 1u << (g.bits[0] + g.bits[1]);  // no query: behind every query
-  if (valid(in, i, x, y, h) && h >= floor)
-    key = (cell_of(clamp(y, g.min[1], g.max[1]), g.min[1], g.edge, g.dim[1]) << g.bits[0]) | cell_of(clamp(x, g.min[0], g.max[0]), g.min[0], g.edge, g.dim[0]);
-  keys[i] = key;
+  keys[i] = valid(in, i, x, y, h) && h >= floor ? query_key(x, y, g) : no_member_key(g);  // (no query: behind every query)
   vals[i] = (uint32_t)i;
 }
 
@@ -300,34 +275,13 @@ __global__ __launch_bounds__(kQ) void trees_crown_kernel(In in, uint32_t nq, Gri
   if (s < nq) {
     const uint32_t i = order[s];
     const uint32_t key = qkeys[s];
-    const uint32_t bx = g.bits[0], by = g.bits[1];
-    if (!(key >> (bx + by))) {  // a query
+    if (is_member_key(key, g)) {  // a query
       double qx, qy, qh;
       load_xyh(in, i, qx, qy, qh);
       Best b{m2, kNone, kNone};
-      const uint32_t cols = g.dim[0], rows = g.dim[1];
-      const uint32_t cx = key & ((1u << bx) - 1u), cy = key >> bx;
-      uint32_t rmax = cx > cols - 1 - cx ? cx : cols - 1 - cx;
-      rmax = max(rmax, cy > rows - 1 - cy ? cy : rows - 1 - cy);
-#pragma unroll 1
-      for (uint32_t r = 1;; ++r) {
-        const uint32_t y0 = cy >= r ? cy - r : 0, y1 = cy + r < rows ? cy + r : rows - 1;
-        const uint32_t x0 = cx >= r ? cx - r : 0, x1 = cx + r < cols ? cx + r : cols - 1;
-#pragma unroll 1
-        for (uint32_t y = y0; y <= y1; ++y) {
-          const uint32_t ay = y > cy ? y - cy : cy - y;
-          const uint32_t row = y * cols;  // below 2^26
-          if (r == 1 || ay == r) {  // a face row of the ring (ring 1 takes ring 0 along): the whole range
-            scan(xs, ys, index, dir[row + x0], dir[row + x1 + 1], qx, qy, b);
-          } else {  // an inner row: the two end cells, where the grid has them
-            if (cx >= r) scan(xs, ys, index, dir[row + cx - r], dir[row + cx - r + 1], qx, qy, b);
-            if (cx + r < cols) scan(xs, ys, index, dir[row + cx + r], dir[row + cx + r + 1], qx, qy, b);
-          }
-        }
-        if (r >= rmax) break;
-        const double reach = (double)r * g.edge_stop;
-        if (b.d2 <= reach * reach) break;
-      }
+      uint32_t cx, cy;
+      cell_of_key(key, g, cx, cy);
+      walk_rings(g, dir, cx, cy, [&](uint32_t first, uint32_t last) { scan(xs, ys, index, first, last, qx, qy, b); }, [&] { return b.d2; });
       if (b.at != kNone) {  // the nearest top first, then its two tests
         const double H = hs[b.at];
         const double rc = half_factor * H;

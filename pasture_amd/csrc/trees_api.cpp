@@ -5,7 +5,7 @@
 #include <cstring>
 #include <limits>
 
-#include "cluster_index.hpp"
+#include "dense_directory.hpp"
 #include "phase_events.hpp"
 
 using namespace pst;
@@ -40,38 +40,28 @@ pstk::HagGrid grid_over(const pstk::TreesBounds& b, double edge, const char* who
   return grid;
 }
 
-// The index of hag.hip over `count` entries (entry e = point subset ? subset[e] : e; the m members first in cell order): the regions of one
-// block of scratch, and the launches.  keys_b holds the sorted keys and `order` the sorted entries afterwards.
-struct TreeIndex {
-  size_t off[9] = {}, sort_bytes = 0, scan_bytes = 0, cells = 0;
-  unsigned key_bits = 0;
-  uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *order = nullptr, *index = nullptr, *dir = nullptr;
+// The dense directory over `count` entries (entry e = point subset ? subset[e] : e; the m members first in cell order) and, in the same
+// block of scratch, the members' x, y, h and buffer index in sorted order.
+struct TreeIndex : DenseDirectory {
+  size_t off_m[4] = {};
+  uint32_t* index = nullptr;
   double *xs = nullptr, *ys = nullptr, *hs = nullptr;
 
   void carve(ScratchLayout& layout, const pstk::HagGrid& grid, size_t count, size_t m, hipStream_t s) {
-    cells = (size_t)grid.dim[0] * grid.dim[1];
-    key_bits = grid.bits[0] + grid.bits[1] + 1;  // (the bit above the cell number: no member)
-    PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_bytes, nullptr, nullptr, nullptr, nullptr, count, key_bits, s, true));
-    PST_HIP_CHECK(pstk::suffix_min_u32(nullptr, scan_bytes, nullptr, cells + 1, s));
-    const size_t bytes[9] = {count * 4, count * 4, count * 4, count * 4, m * 4, (cells + 1) * 4, m * 8, m * 8, m * 8};
-    for (int i = 0; i < 9; ++i) off[i] = layout.add(bytes[i]);
+    DenseDirectory::carve(layout, packed_keys(grid), (size_t)grid.dim[0] * grid.dim[1], count, count, s);
+    const size_t bytes[4] = {m * 4, m * 8, m * 8, m * 8};
+    for (int i = 0; i < 4; ++i) off_m[i] = layout.add(bytes[i]);
   }
-  size_t tmp_bytes() const { return std::max(sort_bytes, scan_bytes); }
   void bind(Scratch& scratch) {
-    keys_a = scratch.at<uint32_t>(off[0]); keys_b = scratch.at<uint32_t>(off[1]); vals_a = scratch.at<uint32_t>(off[2]); order = scratch.at<uint32_t>(off[3]);
-    index = scratch.at<uint32_t>(off[4]); dir = scratch.at<uint32_t>(off[5]);
-    xs = scratch.at<double>(off[6]); ys = scratch.at<double>(off[7]); hs = scratch.at<double>(off[8]);
+    DenseDirectory::bind(scratch);
+    index = scratch.at<uint32_t>(off_m[0]);
+    xs = scratch.at<double>(off_m[1]); ys = scratch.at<double>(off_m[2]); hs = scratch.at<double>(off_m[3]);
   }
-  void build(const pstk::TreesInput& in, const uint32_t* subset, const uint8_t* member, size_t count, uint32_t m, const pstk::HagGrid& grid, void* tmp, hipStream_t s,
-             const char* who) {
-    PST_HIP_CHECK(hipMemsetAsync(dir, 0xFF, (cells + 1) * 4, s));
-    if (!pstk::trees_keys(in.pos, subset, member, count, grid, keys_a, s)) throw hip_failure(std::string(who) + ": key launch failed: ");
-    size_t bytes = sort_bytes;
-    PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, keys_a, keys_b, vals_a, order, count, key_bits, s, true));
-    if (!pstk::trees_gather(in, subset, order, m, xs, ys, hs, index, s)) throw hip_failure(std::string(who) + ": gather launch failed: ");
-    if (!pstk::hag_directory_heads(keys_b, m, grid, dir, s)) throw hip_failure(std::string(who) + ": directory launch failed: ");
-    bytes = scan_bytes;
-    PST_HIP_CHECK(pstk::suffix_min_u32(tmp, bytes, dir, cells + 1, s));
+  // (the heads kernel looks at the m members alone)
+  void build(const pstk::TreesInput& in, const uint32_t* subset, const uint8_t* member, uint32_t m, const pstk::HagGrid& grid, void* tmp, hipStream_t s, const char* who) {
+    DenseDirectory::build(m, tmp, s, who,
+                          [&](uint32_t* keys) { if (!pstk::trees_keys(in.pos, subset, member, count, grid, keys, s)) throw hip_failure(std::string(who) + ": key launch failed: "); },
+                          [&] { if (!pstk::trees_gather(in, subset, order, m, xs, ys, hs, index, s)) throw hip_failure(std::string(who) + ": gather launch failed: "); });
   }
 };
 
@@ -208,7 +198,7 @@ int pst_tree_tops_device(const pst_buffer* b, const double* d_heights, const uin
   uint32_t *flags = scratch.at<uint32_t>(off_flags), *survivors = scratch.at<uint32_t>(off_survivors);
   unsigned long long *offsets = scratch.at<unsigned long long>(off_offsets), *work = scratch.at<unsigned long long>(off_work);
   void* tmp = scratch.at<void>(off_tmp);
-  ix.build(in, nullptr, member, n, nc, grid, tmp, s, who);
+  ix.build(in, nullptr, member, nc, grid, tmp, s, who);
   events.mark(1, s);
   // ---- the filter: the near pass, the survivors' list, the far pass
   PST_HIP_CHECK(hipMemsetAsync(work, 0, sizeof(*work), s));
@@ -296,7 +286,7 @@ int pst_segment_trees_device(const pst_buffer* b, const double* d_heights, const
   TreeIndex ix;
   ix.carve(layout, grid, nt, nt, s);
   size_t sort_q = 0;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_q, nullptr, nullptr, nullptr, nullptr, n, ix.key_bits, s));
+  PST_HIP_CHECK(pstk::sort_pairs_u32(nullptr, sort_q, nullptr, nullptr, nullptr, nullptr, n, ix.keys.bits, s));
   const size_t off_qa = layout.add(n * 4), off_qb = layout.add(n * 4), off_qv = layout.add(n * 4), off_qorder = layout.add(n * 4);
   const size_t off_tmp = layout.add(std::max(ix.tmp_bytes(), sort_q)), off_counts = layout.add((size_t)nt * 4), off_labelled = layout.add(256);
   Scratch scratch(layout, s, who);
@@ -307,10 +297,10 @@ int pst_segment_trees_device(const pst_buffer* b, const double* d_heights, const
   void* tmp = scratch.at<void>(off_tmp);
   PST_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)nt * 4, s));
   PST_HIP_CHECK(hipMemsetAsync(labelled, 0, sizeof(*labelled), s));
-  ix.build(in, numbering.list, nullptr, nt, nt, grid, tmp, s, who);  // (ix.order[s] = the tree number of sorted top s)
+  ix.build(in, numbering.list, nullptr, nt, grid, tmp, s, who);  // (ix.order[s] = the tree number of sorted top s)
   if (!pstk::trees_query_keys(in, min_height, grid, qa, qv, s)) throw hip_failure(std::string(who) + ": query key launch failed: ");
   size_t bytes = sort_q;
-  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, qa, qb, qv, qorder, n, ix.key_bits, s));
+  PST_HIP_CHECK(pstk::sort_pairs_u32(tmp, bytes, qa, qb, qv, qorder, n, ix.keys.bits, s));
   // ---- the search
   if (!pstk::trees_crown_search(in, (uint32_t)n, grid, m2, half_factor, exclusion, qb, qorder, ix.dir, ix.xs, ix.ys, ix.hs, ix.index, ix.order, d_tree_id, counts, labelled, s))
     throw hip_failure(std::string(who) + ": search launch failed: ");

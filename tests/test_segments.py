@@ -308,6 +308,18 @@ def test_no_members_at_all(hip, device_out):
 
 
 @pytest.mark.gpu
+def test_exactly_one_point_without_a_segment(hip):
+    """1 025 points in 3 segments and one of them in none, wherever it stands in the buffer: the only non-member is the last sorted entry,
+    the first lane of a workgroup of its own in the directory's heads kernel, and the member count is its sorted position"""
+    n = 4 * POINTS_PER_BLOCK + 1
+    for at in (0, n // 2, n - 1):
+        labels = (np.arange(n) % 3).astype(np.uint32)
+        labels[at] = NONE
+        got = check(hip, cloud(n, 9), labels, 3, what=f"the point without a segment at {at}")
+        assert got[2] == n - 1 and got[0][0].sum() == n - 1
+
+
+@pytest.mark.gpu
 def test_small_segments(hip):
     """5 000 segments of 1 .. 40 members, shuffled: the regime of the regions"""
     rng = np.random.default_rng(6)
